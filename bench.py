@@ -11,10 +11,19 @@ buffer, inputs already resident in HBM:
     -> decompress_batch (frame decode + XXH32 content-checksum verification)
 
 `value` = uncompressed MB (1e6 B) round-tripped per second, whole job (all ranks).  Per-direction
-rates, per-kernel HIP-event times and the HBM roofline of the kernels ride along, and -- on the
-default single-GPU run -- short legs of the other BASELINE configs under "configs": zstd-mt level 1
-(configs[3]), brotli-mt decompress (configs[4]) and the PCIe-inclusive drop-in APIs (LZ4MT_* /
+rates, per-kernel HIP-event times and the HBM roofline of the kernels (all taken inside the timed
+steps) ride along.  A plain run does nothing else: set-up, warm-up, the timed steps, the decoders'
+status words (decode_errors) and the result line.
+`--full` adds everything measured or checked beyond that: the byte-for-byte comparison of the round
+trip, cpu_baseline (the reference library on the host cores), the brotli leg's device encoder and --
+on the default single-GPU run -- short legs of the other BASELINE configs under "configs": zstd-mt
+level 1 (configs[3]), brotli-mt decompress (configs[4]) and the PCIe-inclusive drop-in APIs (LZ4MT_* /
 ZSTDCB_* / BROTLIMT_* with memcpy callbacks), each with its own roofline / cpu_baseline.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32 /
+float64): the record tables whole, the byte buffers (compressed stream, decompressed output) as a fixed,
+seeded sample of blocks -- the same positions for the same arguments, so that two builds compare output
+for output.
 
 Multi-GPU (`--gpus N`): bench.py starts N ranks itself (torch.distributed.run, one process per GPU,
 RCCL) unless it already runs under a launcher (RANK in the environment, which is how the driver
@@ -69,15 +78,21 @@ def parse():
                     help="--codec snappy: 1 = the batched decoder (zmt_snappy_dec2_kernel), 0 = element by element")
     ap.add_argument("--zstd-level", type=int, default=1,
                     help="--codec zstd: level handed to the device encoder (tiers 1-2 / 3-9 / 10-22); BASELINE configs[3] is 1")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the round trip's byte-for-byte "
+                         "comparison, cpu_baseline, the brotli device-encoder leg and the other configs of the default run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, "
+                         "large buffers as a fixed seeded sample; at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-mib", type=int, default=2048, help="cpu_baseline sample size")
     ap.add_argument("--gather", nargs="?", const="rccl", default="none", choices=("none", "rccl", "d2h"),
                     help="also time the reassembly of the per-rank segments (never part of `value`): rccl = grouped "
                          "send/recv gatherv to rank 0 over xGMI; d2h = every GPU copies its segment to its offset of ONE "
                          "pinned host buffer shared by the ranks, no inter-GPU traffic (SURVEY 8e)")
     ap.add_argument("--no-verify", dest="verify", action="store_false",
-                    help="skip the byte-for-byte comparison of the round trip (on by default)")
-    ap.add_argument("--only", action="store_true", help="main leg only: no zstd / brotli / api legs under 'configs'")
+                    help="--full: skip the byte-for-byte comparison of the round trip (on by default there)")
+    ap.add_argument("--only", action="store_true", help="--full: main leg only, no zstd / brotli / api legs under 'configs'")
     ap.add_argument("--extra-gib", type=float, default=8.0,
                     help="size of the extra legs (zstd / brotli / snappy) of the default run: BASELINE's 8 GiB")
     ap.add_argument("--api-gib", type=float, default=8.0, help="input size of the drop-in API legs of the default run")
@@ -89,7 +104,12 @@ def parse():
     ap.add_argument("--master-port", type=int, default=0)
     ap.add_argument("--dry-run", action="store_true",
                     help="start the ranks, report who runs where (gloo, no GPU touched) and exit")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1")
+    return args
 
 
 def tools():
@@ -243,6 +263,43 @@ def generate(ctx, n, corpus_off):
     return d_in, time.time() - t0
 
 
+DUMP_BLOCKS, DUMP_BLOCK = 1024, 4096   # sample of a byte buffer: 4 MiB of it -> 16 MiB of float32
+DUMP_TABLE = 1 << 19                   # sample of a longer record table: 512 Ki entries -> 4 MiB of float64
+DUMP_LIMIT = 64 * 10**6               # array bytes of one dump in all
+
+
+def dump_outputs(ctx, tables, buffers):
+    """--dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy.  Samples are drawn
+    from generators seeded with SEED (sorted positions, the same for the same size), so the same arguments dump
+    the same positions.
+    tables:  name -> (device buffer, count, numpy dtype) as float64 (offsets reach 2^33): whole up to DUMP_TABLE
+             entries (every default configuration), else DUMP_TABLE sampled entries
+    buffers: name -> (device buffer, bytes) as float32: whole when small, else DUMP_BLOCKS sampled blocks of
+             DUMP_BLOCK bytes"""
+    out_dir, eng = ctx.args.dump_outputs, ctx.eng
+    if not out_dir:
+        return
+    if ctx.world != 1:
+        raise SystemExit("--dump-outputs runs on one GPU")
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name, (d, count, dtype) in tables.items():
+        a = eng.download(d, count * np.dtype(dtype).itemsize, dtype)
+        if count > DUMP_TABLE:
+            a = a[np.sort(np.random.default_rng(SEED).choice(count, DUMP_TABLE, replace=False))]
+        arrays[name] = a.astype(np.float64)
+    for name, (d, nbytes) in buffers.items():
+        if nbytes <= DUMP_BLOCKS * DUMP_BLOCK:
+            arrays[name] = eng.download(d, nbytes).astype(np.float32)
+            continue
+        offs = np.sort(np.random.default_rng(SEED).integers(0, nbytes - DUMP_BLOCK + 1, DUMP_BLOCKS))
+        arrays[name] = np.stack([eng.download(d, DUMP_BLOCK, offset=int(o)) for o in offs]).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def bench_lz4_zstd(ctx, codec, gib_args=None, steps=None, warmup=None, cpu=True, main=True, dec_only=None):
     """configs[1] (lz4), configs[2] (lz4 --mode decompress), configs[3] (zstd)"""
     args, eng, rank, world, dist = ctx.args, ctx.eng, ctx.rank, ctx.world, ctx.dist
@@ -333,8 +390,15 @@ def bench_lz4_zstd(ctx, codec, gib_args=None, steps=None, warmup=None, cpu=True,
     total_c = int(eng.download(d_ro, 8, np.uint64, offset=nrec * 8)[0])
     status = eng.download(d_st, nrec * 4, np.uint32)
     bad = int(ctx.sum_over_ranks(float((status != 0).sum())))
+    if main:
+        dec_tables = {"output_lengths": (d_ol, nrec, np.uint32), "output_offsets": (d_oo, nrec + 1, np.uint64),
+                      "status": (d_st, nrec, np.uint32)}
+        enc_tables = {} if dec_only else {"record_lengths": (d_rl, nrec, np.uint32),
+                                          "record_offsets": (d_ro, nrec + 1, np.uint64)}
+        dump_outputs(ctx, {**enc_tables, **dec_tables},
+                     {"output": (d_out, n), **({} if dec_only else {"stream": (d_stream, total_c)})})
     ok = None
-    if args.verify:
+    if args.verify and args.full:
         ok = ctx.all_true(eng.equal(d_in, d_out, n))
 
     gather_ms = None
@@ -434,7 +498,7 @@ def bench_lz4_zstd(ctx, codec, gib_args=None, steps=None, warmup=None, cpu=True,
         res["roofline_decompress_parse_kernel"] = roof(k_parse, ms["k_dec_parse"], Cb, (k_parse,))
     if gather_ms is not None:
         res["value_with_gather"] = round(U_all / 1e6 / (step_s + gather_ms * 1e-3), 1)
-    if cpu and not args.no_cpu and world == 1:
+    if cpu and args.full and not args.no_cpu and world == 1:
         res["cpu_baseline"] = cpu_baseline(codec, chunk, args.cpu_mib)
     return res
 
@@ -682,8 +746,11 @@ def bench_brotli(ctx, gib_args=None, steps=None, warmup=None, cpu=True, main=Tru
     olen = eng.download(d_ol, nrec * 4, np.uint32)
     bad = int((status != 0).sum())
     U = float(olen.astype(np.uint64).sum())
-    # content check of the first replica (always: it is 1 GiB at most)
-    ok = bad == 0 and int(U) == n
+    if main:
+        dump_outputs(ctx, {"output_lengths": (d_ol, nrec, np.uint32), "status": (d_st, nrec, np.uint32)},
+                     {"output": (d_out, total_cap)})
+    # content check of the first replica (--full: always, it is 1 GiB at most)
+    ok = (bad == 0 and int(U) == n) if args.full else None
     if ok:
         got = eng.download(d_out, base_n)              # capacities == chunk sizes for full chunks
         ok = bool((got == text).all()) if int(out_off[nb]) == base_n else None
@@ -694,7 +761,7 @@ def bench_brotli(ctx, gib_args=None, steps=None, warmup=None, cpu=True, main=Tru
     # ---- the device encoder on the same text (not part of `value`: configs[4] is decompress) ----
     own = None
     try:
-        if args.no_encoder or not main or world > 1:
+        if args.no_encoder or not args.full or not main or world > 1:
             raise RuntimeError("skipped")
         d_text = eng.alloc(n + 64)
         bufs.append(d_text)
@@ -778,7 +845,7 @@ def bench_brotli(ctx, gib_args=None, steps=None, warmup=None, cpu=True, main=Tru
         "decode_errors": bad_all, "roundtrip_verified": ok_all,
         "gen_s": round(gen_s, 2), "device": eng.name,
     }
-    if cpu and not args.no_cpu and world == 1:
+    if cpu and args.full and not args.no_cpu and world == 1:
         res["cpu_baseline"] = cpu_baseline("brotli", chunk, args.cpu_mib)
     return res
 
@@ -843,7 +910,11 @@ def bench_snappy(ctx, gib_args=None, steps=None, warmup=None, main=True):
     ms = {k: v / args.steps for k, v in acc.items()}
     total_c = int(eng.download(d_ro, 8, np.uint64, offset=nrec * 8)[0])
     bad = int((eng.download(d_st, nrec * 4, np.uint32) != 0).sum())
-    ok = bool(eng.equal(d_in, d_out, n)) if args.verify else None
+    if main:
+        dump_outputs(ctx, {"record_lengths": (d_rl, nrec, np.uint32), "record_offsets": (d_ro, nrec + 1, np.uint64),
+                           "output_lengths": (d_ol, nrec, np.uint32), "status": (d_st, nrec, np.uint32)},
+                     {"stream": (d_stream, total_c), "output": (d_out, n)})
+    ok = bool(eng.equal(d_in, d_out, n)) if args.verify and args.full else None
     for b in bufs:
         b.free()
     U, Cb = float(n), float(total_c)
@@ -1034,7 +1105,7 @@ def main():
     else:
         res = bench_lz4_zstd(ctx, args.codec)
 
-    default_run = (world == 1 and args.codec == "lz4" and args.mode == "roundtrip" and not args.only)
+    default_run = (args.full and world == 1 and args.codec == "lz4" and args.mode == "roundtrip" and not args.only)
     if rank == 0 and default_run:
         # the other BASELINE configs, short, in the same line
         cfgs = {}

@@ -9,5 +9,5 @@ print(sys.argv[1], "zstd", d["value"], d["config"].get("ratio"), d["kernels"], d
 PY
 for L in "$@"; do
   if [ $L = base ]; then unset ZMT_LIB; else export ZMT_LIB=$GRAFT_REPO_ROOT/zstdmt_amd/lib/variants/$L.so; fi
-  python bench.py --only --codec zstd --steps 3 --warmup 1 --no-cpu 2>&1 | grep "^DETAIL" | sed "s/^DETAIL //" | python /tmp/zab.py $L
+  python bench.py --full --only --codec zstd --steps 3 --warmup 1 --no-cpu 2>&1 | grep "^DETAIL" | sed "s/^DETAIL //" | python /tmp/zab.py $L
 done
