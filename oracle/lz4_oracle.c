@@ -249,23 +249,50 @@ last_literals:
 }
 
 /* ------------------------------- LZ4 block decoder ------------------------------- */
+/*
+ * End-of-block rules of liblz4 1.9.3's LZ4_decompress_safe (what LZ4F_decompress runs per block, with the
+ * frame's block maximum as capacity), restated on positions: t = the token's input position, ip = input
+ * position after the literal-length bytes, op = output position at the token, all relative to the block;
+ * iend = the block's size, oend = the block maximum.  A sequence that is not the block's last is rejected when
+ *   - its literals end in the last 12 bytes of the capacity: op + lit > oend - 12;
+ *   - its literals end in the last 8 input bytes, unless liblz4 copied them through its shortcut (run below 15,
+ *     token before iend - 16, op <= oend - 32): ip + lit > iend - 8;
+ *   - its match-length bytes end in the last 4 input bytes;
+ *   - its match ends in the last 5 bytes of the capacity, unless the shortcut copied it too (as above, and a
+ *     match-length nibble below 15, offset >= 8).
+ * This is the verdict of LZ4F decoding straight into the caller's buffer (the earlier output as prefix); when that
+ * buffer has less than a block maximum of room, LZ4F decodes into its own buffer with the earlier output as an
+ * external dictionary and the shortcut does not take a match reaching into it -- not modelled (lz4_common.h).
+ * liblz4's fast and safe decoding loops differ, but on these positions they agree (tests/test_oracle_golden.py
+ * checks this restatement against liblz4 over the streams of tests/lz4_synth.py).
+ */
+static int lz4_tail_bad(size_t t, size_t ip, size_t lit, size_t op, size_t iend, size_t oend)
+{
+	const int shortcut = lit < 15 && t + 1 + 16 < iend && op + 32 <= oend;
+	return op + lit + 12 > oend || (!shortcut && ip + lit + 8 > iend);
+}
+
 size_t zo_lz4_block_decode(const uint8_t *src, size_t slen, uint8_t *out, size_t opos,
-			   size_t out_limit)
+			   size_t out_limit, size_t blkmax)
 {
 	const uint8_t *ip = src, *const iend = src + slen;
+	const size_t opos0 = opos;
 
 	if (slen == 0)
 		return (size_t)-1;
 	for (;;) {
 		unsigned tok;
-		size_t lit, ml, off;
+		size_t lit, ml, off, t;
 
 		if (ip >= iend)
 			return (size_t)-1;
+		t = (size_t)(ip - src);
 		tok = *ip++;
 		lit = tok >> 4;
 		if (lit == 15) {
 			unsigned b;
+			if (iend - ip <= 15)
+				return (size_t)-1; /* liblz4 reads no literal-length byte in the last 15 */
 			do {
 				if (ip >= iend)
 					return (size_t)-1;
@@ -274,6 +301,9 @@ size_t zo_lz4_block_decode(const uint8_t *src, size_t slen, uint8_t *out, size_t
 			} while (b == 255);
 		}
 		if ((size_t)(iend - ip) < lit || out_limit - opos < lit)
+			return (size_t)-1;
+		if ((size_t)(iend - ip) > lit &&
+		    lz4_tail_bad(t, (size_t)(ip - src), lit, opos - opos0, slen, blkmax))
 			return (size_t)-1;
 		memcpy(out + opos, ip, lit);
 		ip += lit;
@@ -293,10 +323,16 @@ size_t zo_lz4_block_decode(const uint8_t *src, size_t slen, uint8_t *out, size_t
 				b = *ip++;
 				ml += b;
 			} while (b == 255);
+			if (iend - ip < LASTLITERALS)
+				return (size_t)-1;
 		}
 		ml += MINMATCH;
 		if (off == 0 || off > opos || out_limit - opos < ml)
 			return (size_t)-1;
+		if (opos - opos0 + ml + LASTLITERALS > blkmax &&
+		    !((tok >> 4) < 15 && t + 1 + 16 < slen && opos - opos0 - lit + 32 <= blkmax &&
+		      (tok & 15) < 15 && off >= 8))
+			return (size_t)-1; /* the match ends in the last 5 bytes of the capacity */
 		{
 			size_t i;
 			const uint8_t *m = out + opos - off;
@@ -416,7 +452,7 @@ size_t zo_lz4f_decompress(const uint8_t *src, size_t slen, uint8_t *dst, size_t 
 			size_t base = indep ? opos : 0;
 			size_t room = cap - opos < blkmax ? cap - opos : blkmax;
 			size_t np = zo_lz4_block_decode(ip, bsz, dst + base, opos - base,
-							opos - base + room);
+							opos - base + room, blkmax);
 			if (np == (size_t)-1)
 				return (size_t)-1;
 			opos = np + base;

@@ -53,11 +53,12 @@ size_t zo_lz4_block_encode(zo_lz4_table *t, const uint8_t *chunk, size_t pos, si
 
 /*
  * Decode one LZ4 block into out[opos, ...).  Matches may reach back to out[0] (linked blocks);
- * `out_limit` is the highest position that may be written (opos + 64 KiB or the content size).
+ * `out_limit` is the highest position that may be written (opos + 64 KiB or the content size);
+ * `blkmax` is the frame's block maximum, the capacity liblz4's end-of-block rules are measured from.
  * Returns the new output position, or (size_t)-1 on malformed input.
  */
 size_t zo_lz4_block_decode(const uint8_t *src, size_t slen, uint8_t *out, size_t opos,
-			   size_t out_limit);
+			   size_t out_limit, size_t blkmax);
 
 /* LZ4F_compressFrameBound for the prefs of lib/lz4-mt_compress.c:141-146. */
 size_t zo_lz4f_bound(size_t n);

@@ -76,8 +76,9 @@ def walk_records(stream: bytes):
     return np.array(offs, np.uint64), np.array(lens, np.uint32)
 
 
-def decompress(stream: bytes, variant: int = 0, rec=None):
-    """-> (content bytes, status[n]); variant 0 | ring << 4 = frames + parse4 + copy3 kernels (ring 12 if omitted), 1 = serial decoder"""
+def decompress(stream: bytes, variant: int = 0, rec=None, layout=False):
+    """-> (content bytes, status[n]); variant 0 | ring << 4 = frames + parse4 + copy3 kernels (ring 12 if omitted), 1 = serial decoder.
+    layout=True adds out_off[n + 1] (where each record's output sits) and out_len[n] (what each record decoded to)"""
     L = lib()
     ro, rl = rec if rec is not None else walk_records(stream)
     nrec = len(ro)
@@ -92,6 +93,8 @@ def decompress(stream: bytes, variant: int = 0, rec=None):
                                C.c_uint32(nrec), _p(out), C.c_uint64(total), _p(out_off), _p(out_len),
                                _p(status))
     assert (out[total:] == 0xCC).all(), "decoder wrote past the end of its output"
+    if layout:
+        return out[:total].tobytes(), status, out_off, out_len
     return out[:total].tobytes(), status
 
 

@@ -1,5 +1,6 @@
 """Pin the oracle (CPU restatement) to the reference: committed golden vectors produced by the
 reference's own lz4-mt sources (tests/golden/gen_golden.py) and SURVEY.md Appendix C answers."""
+import ctypes as C
 import json
 import os
 
@@ -155,3 +156,49 @@ def test_oracle_hc_matches_reference_golden(name, level):
     if "out_hex" in e:
         assert s.hex() == e["out_hex"]
     assert H.oracle_decompress(s, max(len(data), 65536)) == data
+
+
+# ---- hand-built sequence streams (tests/lz4_synth.py) against liblz4's recorded verdicts ----
+@pytest.fixture(scope="module")
+def synth():
+    """-> (the cases of tests/lz4_synth.py, their manifest entries)"""
+    import lz4_synth as S
+    with open(os.path.join(H.GOLDEN_DIR, "lz4_synth", "manifest.json")) as f:
+        man = json.load(f)
+    c = S.families(man["seed"])
+    assert sorted(c) == sorted(man["cases"])
+    for n, e in c.items():
+        assert S.sha256(e["frame"]) == man["cases"][n]["frame_sha256"], n
+    return c, man["cases"]
+
+
+def test_oracle_synth_verdicts(synth):
+    """oracle/lz4_oracle.c's LZ4F frame decoder gives liblz4 1.9.3's verdict and bytes on every hand-built stream of
+    tests/lz4_synth.py (end-of-block rules, empty stored blocks, offsets at the edges, malformed blocks)"""
+    synth_cases, syn = synth
+    lib = H.oracle()
+    bad = []
+    for n in sorted(synth_cases):
+        fr = synth_cases[n]["frame"]
+        cap = 1 << 23
+        buf = C.create_string_buffer(cap)
+        r = lib.zo_lz4f_decompress(fr, len(fr), buf, cap)
+        m = syn[n]
+        acc = r != H.SIZE_ERR
+        if acc != (m["liblz4"] == "accept") or (acc and H.sha256(buf.raw[:r]) != m["content_sha256"]):
+            bad.append((n, acc, m["liblz4"]))
+    assert not bad, bad
+
+
+def test_synth_manifest_is_current(synth):
+    """with liblz4 on the machine: the recorded verdicts are what it says today"""
+    synth_cases, syn = synth
+    import lz4_synth as S
+    if S.liblz4_path() is None:
+        pytest.skip("liblz4 is not on this machine")
+    for n in sorted(synth_cases):
+        ok, data = S.liblz4_decompress(synth_cases[n]["frame"])
+        m = syn[n]
+        assert ok == (m["liblz4"] == "accept"), n
+        if ok:
+            assert S.sha256(data) == m["content_sha256"], n

@@ -18,6 +18,39 @@ enum {
 	ST_BAD_CHECKSUM = 5, ST_TRAILING = 6, ST_UNSUPPORTED = 7
 };
 
+/*
+ * End-of-block rules of liblz4 1.9.3's LZ4_decompress_safe, which LZ4F_decompress runs per block with the frame's
+ * block maximum as capacity (the reference's decoder calls it per record), restated on positions relative to
+ * the block: t = a token's input position, ip = the input position after its literal-length bytes,
+ * op = the output position at the token, iend = the block's compressed size, oend = the block maximum.
+ * A sequence that is NOT the block's last is malformed when
+ *   - its literals end in the last 12 bytes of the capacity (op + lit > oend - 12), or in the last 8 input bytes
+ *     (ip + lit > iend - 8) unless liblz4 took its shortcut: run below 15, t + 1 < iend - 16, op <= oend - 32;
+ *   - its match-length bytes end in the last 4 input bytes (checked where they are read);
+ *   - its match ends in the last 5 bytes of the capacity, unless the shortcut copied it too (as above, and a
+ *     match-length nibble below 15 and an offset of 8 or more).
+ * This is liblz4's verdict when LZ4F_decompress decodes the block straight into the caller's buffer, the earlier output
+ * being its prefix.  Where that buffer has less than a block maximum of room left, LZ4F decodes into its own buffer
+ * with the earlier output as an external dictionary; there the shortcut does not copy a match that reaches into the
+ * dictionary, so such a match ending in the capacity's last 5 bytes is rejected as well.  That case (the last block
+ * of a linked frame, such a match ending at block output 65531..65535) is not modelled.
+ * A literal-length byte in the last 15 input bytes is malformed too.  liblz4's fast and safe loops differ in
+ * control flow but agree on these positions (tests/test_oracle_golden.py checks oracle/lz4_oracle.c, which
+ * restates the same rules, against liblz4 over tests/lz4_synth.py's streams).
+ */
+static __device__ __forceinline__ bool lz4lib_tail_bad(u32 t, u32 ip, u32 lit, u32 op, u32 iend, u32 oend)
+{
+	const bool shortcut = lit < 15u && t + 17u < iend && op + 32u <= oend;
+	return op + lit + 12u > oend || (!shortcut && ip + lit + 8u > iend);
+}
+/* the match rule: tok = the token byte, op = output position at the token, len = literals + match */
+static __device__ __forceinline__ bool lz4lib_match_tail_bad(u32 t, u32 tok, u32 off, u32 op, u32 len, u32 iend,
+							      u32 oend)
+{
+	const bool shortcut = tok < 0xF0u && t + 17u < iend && op + 32u <= oend && (tok & 15u) != 15u && off >= 8u;
+	return op + len + 5u > oend && !shortcut;
+}
+
 #define XP1 2654435761u
 #define XP2 2246822519u
 #define XP3 3266489917u

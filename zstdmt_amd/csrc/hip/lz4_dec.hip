@@ -18,22 +18,28 @@
 
 /*
  * Decode one LZ4 block [src, src+slen) appending at out[opos...]; matches may reach back to
- * out[low].  Returns new opos or 0xFFFFFFFF on malformed input.  limit = highest legal opos.
+ * out[low].  Returns new opos or 0xFFFFFFFF on malformed input.  limit = highest legal opos,
+ * blkmax = the frame's block maximum: liblz4's end-of-block rules (lz4lib_tail_bad, lz4_common.h)
+ * are measured from it.
  */
 static __device__ u32 decode_block_serial(const u8 *src, u32 slen, u8 *out, u32 opos, u32 low,
-					  u32 limit, int lane)
+					  u32 limit, u32 blkmax, int lane)
 {
 	u32 ip = 0;
+	const u32 opos0 = opos;
 	if (slen == 0)
 		return 0xFFFFFFFFu;
 	for (;;) {
-		u32 tok, lit, ml, off;
+		u32 tok, lit, ml, off, t;
 		if (ip >= slen)
 			return 0xFFFFFFFFu;
+		t = ip;
 		tok = uld8(src + ip++);
 		lit = tok >> 4;
 		if (lit == 15) {
 			u32 b;
+			if (slen - ip <= 15)
+				return 0xFFFFFFFFu;
 			do {
 				if (ip >= slen)
 					return 0xFFFFFFFFu;
@@ -42,6 +48,8 @@ static __device__ u32 decode_block_serial(const u8 *src, u32 slen, u8 *out, u32 
 			} while (b == 255);
 		}
 		if (slen - ip < lit || limit - opos < lit)
+			return 0xFFFFFFFFu;
+		if (slen - ip > lit && lz4lib_tail_bad(t, ip, lit, opos - opos0, slen, blkmax))
 			return 0xFFFFFFFFu;
 		wave_copy(out + opos, src + ip, lit, lane);
 		ip += lit;
@@ -61,9 +69,13 @@ static __device__ u32 decode_block_serial(const u8 *src, u32 slen, u8 *out, u32 
 				b = uld8(src + ip++);
 				ml += b;
 			} while (b == 255);
+			if (slen - ip < 5)
+				return 0xFFFFFFFFu;
 		}
 		ml += 4;
 		if (off == 0 || off > opos - low || limit - opos < ml)
+			return 0xFFFFFFFFu;
+		if (lz4lib_match_tail_bad(t, tok, off, opos - opos0 - lit, lit + ml, slen, blkmax))
 			return 0xFFFFFFFFu;
 		wave_mem_fence();
 		{
@@ -169,7 +181,7 @@ zmt_lz4_dec_serial(const u8 *__restrict__ stream, const u64 *__restrict__ rec_of
 		} else {
 			u32 room = cap - opos < fi.blkmax ? cap - opos : fi.blkmax;
 			u32 np = decode_block_serial(r + ip, bsz, out, opos, fi.indep ? opos : 0,
-						     opos + room, lane);
+						     opos + room, fi.blkmax, lane);
 			if (np == 0xFFFFFFFFu) {
 				st = ST_BAD_BLOCK;
 				goto done;

@@ -26,7 +26,8 @@
  *     quad broadcasts (parse3: ds_bpermute), twice 4 loads every 8 steps;
  *   - token positions leave through a 16-entry tile per lane at wave-uniform points (every 8 steps, with the
  *     refill), so the store is not re-tested every step;
- *   - the loop's exit test runs every 8 steps.
+ *   - the loop's exit test runs every 8 steps;
+ *   - liblz4's end-of-block rules are checked once per block behind the walk, on the last few tokens.
  *
  * Blocks whose wave-relative position does not fit 31 bits (records far apart in a caller-supplied layout; the host
  * engines never produce one) are walked token by token through the global-memory path: slow, correct, no sentinel
@@ -269,6 +270,49 @@ zmt_dec_parse4_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const u64
 	}
 	if (opos > ZMT_BLOCK)
 		ok = false;
+	/* liblz4's end-of-block rules (lz4lib_tail_bad, lz4_common.h) concern only the sequences in front of the last
+	 * whose match ends in the block's last 6 input bytes or in the capacity's last 12 output bytes: at most five (3
+	 * input bytes, 4 output bytes per sequence), all still in the lane's 16-entry tile.  They are checked here, once
+	 * per block, walking back from the last sequence, so the step carries none of it */
+	if (parse && ok && n >= 2u) {
+		u32 tn = mytile[(n - 1u) & 15u], t = src[tn], lt = t >> 4, h = tn + 1u;
+		if (lt == 15u) {
+			u32 b;
+			do {
+				b = src[h++];
+				lt += b;
+			} while (b == 255u);
+		}
+		u32 oat = opos - lt; /* output position at token tn */
+		for (u32 k = n - 1u; k > 0u && n - k < 16u && (tn + 6u > cs || oat + 12u > ZMT_BLOCK); k--) {
+			const u32 tq = mytile[(k - 1u) & 15u];
+			t = src[tq];
+			u32 l2 = t >> 4, m2 = t & 15u, q = tq + 1u;
+			if (l2 == 15u) {
+				u32 b;
+				do {
+					b = src[q++];
+					l2 += b;
+				} while (b == 255u);
+			}
+			const u32 lend = q + l2, off = (u32)src[lend] | (u32)src[lend + 1u] << 8;
+			if (m2 == 15u) {
+				u32 b, m = lend + 2u;
+				do {
+					b = src[m++];
+					m2 += b;
+				} while (b == 255u);
+				if (m + 5u > cs)
+					ok = false;
+			}
+			m2 += 4u;
+			const u32 op = oat - l2 - m2;
+			if (lz4lib_tail_bad(tq, q, l2, op, cs, ZMT_BLOCK) || lz4lib_match_tail_bad(tq, t, off, op, l2 + m2, cs, ZMT_BLOCK))
+				ok = false;
+			oat = op;
+			tn = tq;
+		}
+	}
 	if (exists) {
 		if (parse) {
 			blk_ntok[gb] = ok ? n : 0;

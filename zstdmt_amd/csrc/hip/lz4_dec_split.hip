@@ -124,7 +124,9 @@ zmt_dec_frames_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec
 		if (bh == 0)
 			break;
 		bsz = bh & 0x7FFFFFFFu;
-		if (bsz > ZMT_BLOCK || flen - ip < bsz || bsz == 0) {
+		/* (a compressed block cannot have size 0 -- its header would be the end mark --, a stored one can: liblz4
+		 * decodes the empty stored block 0x80000000) */
+		if (bsz > ZMT_BLOCK || flen - ip < bsz) {
 			st = ST_BAD_BLOCK;
 			break;
 		}
