@@ -1,18 +1,16 @@
 /* CPU harness for the host-side frame splitters of the plain-stream paths (tests/test_host_extent.py):
- * lz4_frame_extent (lz4mt_engine.c) and zstd_frame_extent (zstdmt_engine.c) are static, so the engine
- * sources are included here; nothing that touches the device is called (linked with unresolved
- * gpumt_* symbols ignored).
+ * lz4_frame_extent and zstd_frame_extent of zstdmt_amd/csrc/host/mt_frame_extent.h, which needs nothing of the
+ * device boundary.
  *   extent_harness lz4|zstd FILE      -> one line per frame: offset length bound flag
  *   extent_harness lz4|zstd FILE cut  -> number of proper prefixes of the first frame that are (wrongly)
  *                                        accepted as a complete frame: must print 0 */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include "../../zstdmt_amd/csrc/host/mt_frame_extent.h"
 #ifdef HARNESS_ZSTD
-#include "../../zstdmt_amd/csrc/host/zstdmt_engine.c"
 #define EXTENT zstd_frame_extent
 #else
-#include "../../zstdmt_amd/csrc/host/lz4mt_engine.c"
 #define EXTENT lz4_frame_extent
 #endif
 

@@ -1,5 +1,5 @@
-"""Host-side frame splitting of the plain .lz4 / .zst paths (lz4_frame_extent, zstd_frame_extent in the
-engines) on the CPU: frame lengths equal what liblz4 / libzstd wrote, the capacity bound covers the
+"""Host-side frame splitting of the plain .lz4 / .zst paths (lz4_frame_extent, zstd_frame_extent in
+mt_frame_extent.h) on the CPU: frame lengths equal what liblz4 / libzstd wrote, the capacity bound covers the
 content, and no proper prefix of a frame is mistaken for a complete one (the incremental reader relies
 on that to wait for more input)."""
 import os
@@ -15,12 +15,9 @@ HOST = os.path.join(H.ROOT, "tests", "host")
 
 def build(kind):
     exe = os.path.join(HOST, "extent_harness_" + kind)
-    subprocess.check_call(["gcc", "-O1", "-g", "-pthread", "-w", "-I" + os.path.join(H.ROOT, "include"),
-                           "-I" + os.path.join(H.ROOT, "zstdmt_amd", "csrc", "host")]
+    subprocess.check_call(["gcc", "-O1", "-g", "-Wall", "-Wextra"]
                           + (["-DHARNESS_ZSTD"] if kind == "zstd" else [])
-                          + [os.path.join(HOST, "extent_harness.c"),
-                             os.path.join(H.ROOT, "zstdmt_amd", "csrc", "host", "mt_pipe.c"),
-                             "-Wl,--unresolved-symbols=ignore-all", "-o", exe])
+                          + [os.path.join(HOST, "extent_harness.c"), "-o", exe])
     return exe
 
 

@@ -6,7 +6,7 @@
  * snappymt_engine.c with
  *
  *   MTP(x)                    <PREFIX>_##x
- *   MT_CODEC                  "brotli" / "snappy" (the default error string)
+ *   MT_CODEC                  "brotli" / "snappy" (the default error string, the trace lines)
  *   MT_LEVEL_OK(level)        createCCtx's level check
  *   MT_DEFAULT_CHUNK(level)   chunk size for inputsize == 0
  *   MT_SLOT_STRIDE(chunk)     bytes a record can occupy
@@ -23,7 +23,8 @@
  * payload in one read, one fn_write per record in order; a stream that does not decode into its
  * capacity fails with frame_decompress.  Records move through the same three-role batch pipeline as
  * the other codecs (mt_pipe.h): H2D / decode kernel / D2H on three streams.
- * Compression: pt_compress behaviour over the device encoder, see below.
+ * Compression: pt_compress behaviour over the device encoder, mt_compress.inc (shared with lz4mt_engine.c and
+ * zstdmt_engine.c).
  * Plain C, no HIP header.
  */
 #include "mt_host.h"
@@ -37,243 +38,22 @@ unsigned MTP(isError)(size_t code)
 
 const char *MTP(getErrorString)(size_t code)
 {
-	/* strings of lib/brotli-mt_common.c:37-57 */
-	switch ((MTP(ErrorCode))((size_t)0 - code)) {
-	case MTP(error_no_error):
-		return "No error detected";
-	case MTP(error_memory_allocation):
-		return "Allocation error : not enough memory";
-	case MTP(error_read_fail):
-		return "Read failure";
-	case MTP(error_write_fail):
-		return "Write failure";
-	case MTP(error_data_error):
-		return "Malformed input";
-	case MTP(error_frame_compress):
-		return "Could not compress frame at once";
-	case MTP(error_frame_decompress):
-		return "Could not decompress frame at once";
-	case MTP(error_compressionParameter_unsupported):
-		return "Compression parameter is out of bound";
-	default:
-		return "Unspecified " MT_CODEC " error code";
-	}
-}
-
-/* callback return value -> library error (mt_error, brotli-mt_decompress.c:142-155) */
-static size_t mt_error(int rv)
-{
-	switch (rv) {
-	case -1:
-		return MTP(ERROR)(read_fail);
-	case -2:
-		return MTP(ERROR)(canceled);
-	case -3:
-		return MTP(ERROR)(memory_allocation);
-	}
-	return MTP(ERROR)(read_fail);
+	/* strings of lib/brotli-mt_common.c:37-57: compression_library and canceled have none there */
+	const size_t idx = (size_t)0 - code;
+	return idx < MTP(error_compression_library) ? mt_error_name(idx) : "Unspecified " MT_CODEC " error code";
 }
 
 /* =================================================================== compression
- * pt_compress of the reference (lib/brotli-mt_compress.c:194-318): one fn_read of exactly
- * `inputsize` per chunk, EOF = a zero-length read once a frame exists (an empty input still yields
- * one record), a short read becomes a short record and the loop goes on; one fn_write per record
- * in order: 16-byte header (hint = 64 KiB units of output, :294-304) + one codec stream.  The streams
- * come from the device encoder (MT_COMPRESS_BATCH) and are decompress-identical to the input; `level`
- * is validated and sets the default chunk size where the reference does so. */
-struct cslot {
-	dbuf in;      /* chunk data, H2D                       */
-	dbuf slots;   /* device only: per-chunk records        */
-	dbuf stream;  /* packed records, D2H                   */
-	dbuf meta;    /* rec_len[n] u32 | pad | rec_off[n+1] u64, D2H */
-	size_t n;     /* bytes in the batch                    */
-	size_t nrec;
-};
+ * mt_compress.inc, with what brotli-mt and snappy-mt have in common.  One fn_write per record: 16-byte header
+ * (hint = 64 KiB units of output, lib/brotli-mt_compress.c:294-304) + one codec stream; the streams are
+ * decompress-identical to the input. */
+#define MT_BATCH_UNIT(chunk) (chunk)
+#define MT_C_DEVICE_ERROR frame_compress
+#define MT_C_NULL_CTX compressionParameter_unsupported /* brotli-mt_compress.c:325-326 */
+#define MT_C_NULL_GET 0
+#define MT_COMPRESS_ENTER(ctx) ((void)(ctx), (size_t)0) /* counters carry over from the last call */
 
-struct MTP(CCtx_s) {
-	int level, threads, inputsize;
-	size_t insize, outsize, curframe, frames; /* insize / frames: reader; outsize / curframe: writer */
-	mt_gpus gpus; /* the devices the batch slots are dealt out to (mt_host.h) */
-	struct cslot s[MT_NSLOT];
-	MTP(RdWr_t) *io;
-	size_t maxrec;
-};
-
-MTP(CCtx) *MTP(createCCtx)(int threads, int level, int inputsize)
-{
-	MTP(CCtx) *ctx;
-	if (threads < 1 || threads > MTP(THREAD_MAX))
-		return NULL;
-	if (!MT_LEVEL_OK(level))
-		return NULL;
-	if (inputsize < 0)
-		return NULL;
-	ctx = (MTP(CCtx) *)calloc(1, sizeof *ctx);
-	if (!ctx)
-		return NULL;
-	ctx->threads = threads;
-	ctx->level = level;
-	ctx->inputsize = inputsize ? inputsize : MT_DEFAULT_CHUNK(level);
-	if (mt_gpus_open(&ctx->gpus)) {
-		free(ctx); /* no device: fail loudly, there is no CPU path */
-		return NULL;
-	}
-	return ctx;
-}
-
-void MTP(freeCCtx)(MTP(CCtx) *ctx)
-{
-	if (!ctx)
-		return;
-	for (int i = 0; i < MT_NSLOT; i++) {
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].in);
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].slots);
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].stream);
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].meta);
-	}
-	mt_gpus_close(&ctx->gpus);
-	free(ctx);
-}
-
-size_t MTP(GetFramesCCtx)(MTP(CCtx) *ctx) { return ctx ? ctx->curframe : 0; }
-size_t MTP(GetInsizeCCtx)(MTP(CCtx) *ctx) { return ctx ? ctx->insize : 0; }
-size_t MTP(GetOutsizeCCtx)(MTP(CCtx) *ctx) { return ctx ? ctx->outsize : 0; }
-
-static size_t c_read_batch(MTP(CCtx) *ctx, MTP(RdWr_t) *io, struct cslot *s, size_t maxrec, int *eof)
-{
-	const size_t chunk = (size_t)ctx->inputsize;
-	s->n = 0;
-	s->nrec = 0;
-	while (s->nrec < maxrec) {
-		MTP(Buffer) b;
-		int rv;
-		b.buf = (uint8_t *)s->in.h + s->n;
-		b.size = chunk;
-		b.allocated = chunk;
-		rv = io->fn_read(io->arg_read, &b);
-		if (rv != 0)
-			return mt_error(rv);
-		if (b.size == 0 && ctx->frames > 0) {
-			*eof = 1;
-			break;
-		}
-		if (b.size > chunk)
-			return MTP(ERROR)(read_fail);
-		ctx->insize += b.size;
-		ctx->frames++;
-		s->n += b.size;
-		s->nrec++;
-		if (b.size < chunk)
-			break; /* ragged chunk: last one of this device batch */
-	}
-	return 0;
-}
-
-static size_t c_launch(MTP(CCtx) *ctx, struct cslot *s)
-{
-	gpumt_ctx *g = mt_gpu_of(&ctx->gpus, (int)(s - ctx->s));
-	const int ks = mt_stream_of(&ctx->gpus, (int)(s - ctx->s)); /* the slot's own kernel stream: batches overlap on the device */
-	const size_t chunk = (size_t)ctx->inputsize;
-	const size_t stride = MT_SLOT_STRIDE(chunk);
-	uint32_t *d_len = (uint32_t *)s->meta.d;
-	uint64_t *d_off = (uint64_t *)((uint8_t *)s->meta.d + ((s->nrec * 4 + 15) & ~(size_t)15));
-	int rc = 0;
-	if (s->n)
-		rc |= gpumt_memcpy_h2d(g, s->in.d, s->in.h, s->n, 1);
-	rc |= gpumt_stream_wait(g, ks, 1);
-	rc |= MT_COMPRESS_BATCH(g, s->in.d, s->n, chunk, s->slots.d, stride, d_len, ctx->level, ks);
-	rc |= gpumt_lz4_compact(g, s->slots.d, stride, d_len, s->nrec, s->stream.d, d_off, ks);
-	/* sizes, offsets and the packed records go to the pinned mirrors from the slot's own stream, the
-	 * byte count of the records read on the device (d_off[nrec]): no host round trip in between, and
-	 * the batches of the pipeline overlap (gpumt_push_host) */
-	rc |= gpumt_push_host(g, s->meta.h, s->meta.d, ((s->nrec * 4 + 15) & ~(size_t)15) + (s->nrec + 1) * 8, NULL, ks);
-	rc |= gpumt_push_host(g, s->stream.h, s->stream.d, s->stream.cap & ~(size_t)15, d_off + s->nrec, ks);
-	return rc ? MTP(ERROR)(frame_compress) : 0;
-}
-
-static void cp_role_start(void *a) { mt_bind_near(&((MTP(CCtx) *)a)->gpus); }
-static size_t cp_fill(void *a, int si, int *has_data, int *eof)
-{
-	MTP(CCtx) *ctx = (MTP(CCtx) *)a;
-	struct cslot *s = &ctx->s[si];
-	const size_t chunk = (size_t)ctx->inputsize, stride = MT_SLOT_STRIDE(chunk);
-	size_t lim = zmt_batch_bytes_for(chunk) / chunk, err;
-	if (lim < 1)
-		lim = 1;
-	if (lim > BATCH_MAXREC)
-		lim = BATCH_MAXREC;
-	if (ctx->maxrec > lim)
-		ctx->maxrec = lim;
-	if (dbuf_want(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->in, ctx->maxrec * chunk + 512, 1, 1) ||
-	    dbuf_want(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->slots, ctx->maxrec * stride, 0, 1) ||
-	    dbuf_want(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->stream, ctx->maxrec * stride + 512, 1, 1) ||
-	    dbuf_want(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->meta, ctx->maxrec * 12 + 64, 1, 1))
-		return MTP(ERROR)(memory_allocation);
-	err = c_read_batch(ctx, ctx->io, s, ctx->maxrec, eof);
-	*has_data = s->nrec > 0;
-	ctx->maxrec *= 4;
-	return err;
-}
-
-static size_t cp_launch(void *a, int si)
-{
-	MTP(CCtx) *ctx = (MTP(CCtx) *)a;
-	size_t err = c_launch(ctx, &ctx->s[si]);
-	if (!err && gpumt_mark(mt_gpu_of(&ctx->gpus, si), mt_mark_of(&ctx->gpus, si), mt_stream_of(&ctx->gpus, si)))
-		err = MTP(ERROR)(frame_compress);
-	return err;
-}
-
-static size_t cp_complete(void *a, int si)
-{
-	MTP(CCtx) *ctx = (MTP(CCtx) *)a;
-	struct cslot *s = &ctx->s[si];
-	const uint64_t *off = (const uint64_t *)((const uint8_t *)s->meta.h + ((s->nrec * 4 + 15) & ~(size_t)15));
-	size_t total;
-	if (gpumt_mark_sync(mt_gpu_of(&ctx->gpus, si), mt_mark_of(&ctx->gpus, si)))
-		return MTP(ERROR)(frame_compress);
-	total = (size_t)off[s->nrec];
-	if (total > s->stream.cap)
-		return MTP(ERROR)(frame_compress);
-	return 0;
-}
-
-static size_t cp_drain(void *a, int si)
-{
-	MTP(CCtx) *ctx = (MTP(CCtx) *)a;
-	struct cslot *s = &ctx->s[si];
-	const uint32_t *len = (const uint32_t *)s->meta.h;
-	const uint64_t *off = (const uint64_t *)((const uint8_t *)s->meta.h + ((s->nrec * 4 + 15) & ~(size_t)15));
-	for (size_t i = 0; i < s->nrec; i++) { /* pt_write: strictly in frame order */
-		MTP(Buffer) b;
-		int rv;
-		b.buf = (uint8_t *)s->stream.h + off[i];
-		b.size = len[i];
-		b.allocated = len[i];
-		rv = ctx->io->fn_write(ctx->io->arg_write, &b);
-		if (rv != 0)
-			return mt_error(rv);
-		ctx->outsize += len[i];
-		ctx->curframe++;
-	}
-	return 0;
-}
-
-size_t MTP(compressCCtx)(MTP(CCtx) *ctx, MTP(RdWr_t) *rdwr)
-{
-	static const mt_pipe_ops ops = {cp_fill, cp_launch, cp_complete, cp_drain, cp_role_start};
-	size_t err;
-
-	if (!ctx)
-		return MTP(ERROR)(compressionParameter_unsupported); /* brotli-mt_compress.c:325-326 */
-	ctx->io = rdwr;
-	ctx->maxrec = BATCH_MIN / (size_t)ctx->inputsize;
-	if (ctx->maxrec < 1)
-		ctx->maxrec = 1;
-	err = mt_pipe_run_n(&ops, ctx, mt_nslot_for(ctx->gpus.n));
-	mt_gpus_sync(&ctx->gpus);
-	return err;
-}
+#include "mt_compress.inc"
 
 /* =================================================================== decompression */
 struct dslot {
@@ -317,12 +97,8 @@ void MTP(freeDCtx)(MTP(DCtx) *ctx)
 {
 	if (!ctx)
 		return;
-	for (int i = 0; i < MT_NSLOT; i++) {
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].in);
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].meta);
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].res);
-		dbuf_free(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].out);
-	}
+	for (int i = 0; i < MT_NSLOT; i++)
+		dbuf_free4(mt_gpu_of(&ctx->gpus, i), &ctx->s[i].in, &ctx->s[i].meta, &ctx->s[i].res, &ctx->s[i].out);
 	mt_gpus_close(&ctx->gpus);
 	free(ctx);
 }
@@ -331,11 +107,8 @@ size_t MTP(GetFramesDCtx)(MTP(DCtx) *ctx) { return ctx ? ctx->curframe : 0; }
 size_t MTP(GetInsizeDCtx)(MTP(DCtx) *ctx) { return ctx ? ctx->insize : 0; }
 size_t MTP(GetOutsizeDCtx)(MTP(DCtx) *ctx) { return ctx ? ctx->outsize : 0; }
 
-#define D_META_BYTES(n) ((n) * 8 + ((n) + 1) * 8 + (n) * 4 + (n) * 4 + 64)
-static uint64_t *m_rec_off(struct dslot *s, int dev) { return (uint64_t *)(dev ? s->meta.d : s->meta.h); }
-static uint64_t *m_out_off(struct dslot *s, int dev) { return m_rec_off(s, dev) + BATCH_MAXREC; }
-static uint32_t *m_rec_len(struct dslot *s, int dev) { return (uint32_t *)(m_out_off(s, dev) + BATCH_MAXREC + 1); }
-static uint32_t *m_out_cap(struct dslot *s, int dev) { return m_rec_len(s, dev) + BATCH_MAXREC; }
+/* the meta arrays of mt_host.h, the fourth one holding capacities here; the decoder's answers are in `res` */
+static uint32_t *m_out_cap(const dbuf *meta, int dev) { return m_out_len(meta, dev); }
 static uint32_t *r_out_len(struct dslot *s, int dev) { return (uint32_t *)(dev ? s->res.d : s->res.h); }
 static uint32_t *r_status(struct dslot *s, int dev) { return r_out_len(s, dev) + BATCH_MAXREC; }
 
@@ -415,18 +188,11 @@ static size_t d_read_batch(MTP(DCtx) *ctx, MTP(RdWr_t) *io, struct dslot *s, int
 		if (s->in_bytes + (size_t)csize + 512 > s->in.cap) {
 			/* the record buffer starts at half the output budget (text shrinks more than 2:1) and
 			 * doubles when a batch needs more */
-			dbuf old = s->in;
 			size_t want = s->in_bytes + (size_t)csize + 512;
-			if (want < 2 * old.cap)
-				want = 2 * old.cap;
-			memset(&s->in, 0, sizeof s->in);
-			if (dbuf_want(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->in, want, 1, 1)) {
-				dbuf_free(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->in);
-				s->in = old; /* keep the slot as it was: freeCtx releases it */
+			if (want < 2 * s->in.cap)
+				want = 2 * s->in.cap;
+			if (dbuf_grow_keep(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &s->in, s->in_bytes, want))
 				return MTP(ERROR)(memory_allocation);
-			}
-			memcpy(s->in.h, old.h, s->in_bytes);
-			dbuf_free(mt_gpu_of(&ctx->gpus, (int)(s - ctx->s)), &old);
 		}
 		b.buf = (uint8_t *)s->in.h + s->in_bytes;
 		b.size = csize;
@@ -458,15 +224,15 @@ static size_t d_read_batch(MTP(DCtx) *ctx, MTP(RdWr_t) *io, struct dslot *s, int
 			cap = ok && v <= 0x7FFFFFFFull && v <= (uint64_t)csize * 22u + 64u ? (size_t)v : 0;
 		}
 #endif
-		m_rec_off(s, 0)[s->nrec] = s->in_bytes;
-		m_rec_len(s, 0)[s->nrec] = csize;
-		m_out_off(s, 0)[s->nrec] = s->out_bytes;
-		m_out_cap(s, 0)[s->nrec] = (uint32_t)cap;
+		m_rec_off(&s->meta, 0)[s->nrec] = s->in_bytes;
+		m_rec_len(&s->meta, 0)[s->nrec] = csize;
+		m_out_off(&s->meta, 0)[s->nrec] = s->out_bytes;
+		m_out_cap(&s->meta, 0)[s->nrec] = (uint32_t)cap;
 		s->in_bytes += csize;
 		s->out_bytes += cap;
 		s->nrec++;
 	}
-	m_out_off(s, 0)[s->nrec] = s->out_bytes;
+	m_out_off(&s->meta, 0)[s->nrec] = s->out_bytes;
 	return 0;
 }
 
@@ -482,8 +248,8 @@ static size_t d_launch(MTP(DCtx) *ctx, struct dslot *s)
 	rc |= gpumt_memcpy_h2d(g, s->in.d, s->in.h, s->in_bytes + 256, 1);
 	rc |= gpumt_memcpy_h2d(g, s->meta.d, s->meta.h, D_META_BYTES(BATCH_MAXREC), 1);
 	rc |= gpumt_stream_wait(g, ks, 1);
-	rc |= MT_DECOMPRESS_BATCH(g, s->in.d, m_rec_off(s, 1), m_rec_len(s, 1), s->nrec, s->out.d,
-					    m_out_off(s, 1), m_out_cap(s, 1), r_out_len(s, 1), r_status(s, 1), ks);
+	rc |= MT_DECOMPRESS_BATCH(g, s->in.d, m_rec_off(&s->meta, 1), m_rec_len(&s->meta, 1), s->nrec, s->out.d,
+					    m_out_off(&s->meta, 1), m_out_cap(&s->meta, 1), r_out_len(s, 1), r_status(s, 1), ks);
 	rc |= gpumt_stream_wait(g, 2, ks);
 	rc |= gpumt_memcpy_d2h(g, s->res.h, s->res.d, BATCH_MAXREC * 8, 2);
 	if (s->out_bytes)
@@ -510,16 +276,16 @@ static size_t dp_fill(void *a, int si, int *has_data, int *eof)
 static size_t dp_launch(void *a, int si)
 {
 	MTP(DCtx) *ctx = (MTP(DCtx) *)a;
+	mt_trace_launch(&ctx->gpus, MT_CODEC "mt decompress", si, ctx->s[si].nrec);
 	size_t err = d_launch(ctx, &ctx->s[si]);
-	if (!err && gpumt_mark(mt_gpu_of(&ctx->gpus, si), mt_mark_of(&ctx->gpus, si), 2))
+	if (!err && mt_slot_mark(&ctx->gpus, si, 2))
 		err = MTP(ERROR)(frame_decompress);
 	return err;
 }
 
 static size_t dp_complete(void *a, int si)
 {
-	MTP(DCtx) *ctx = (MTP(DCtx) *)a;
-	return gpumt_mark_sync(mt_gpu_of(&ctx->gpus, si), mt_mark_of(&ctx->gpus, si)) ? MTP(ERROR)(frame_decompress) : 0;
+	return mt_slot_wait(&((MTP(DCtx) *)a)->gpus, si) ? MTP(ERROR)(frame_decompress) : 0;
 }
 
 static size_t dp_drain(void *a, int si)
@@ -532,9 +298,9 @@ static size_t dp_drain(void *a, int si)
 		int rv;
 		if (st[i] != GPUMT_ST_OK)
 			return MTP(ERROR)(frame_decompress); /* pt_decompress :348-351 */
-		b.buf = (uint8_t *)s->out.h + m_out_off(s, 0)[i];
+		b.buf = (uint8_t *)s->out.h + m_out_off(&s->meta, 0)[i];
 		b.size = ol[i];
-		b.allocated = m_out_cap(s, 0)[i];
+		b.allocated = m_out_cap(&s->meta, 0)[i];
 		rv = ctx->io->fn_write(ctx->io->arg_write, &b);
 		if (rv != 0)
 			return mt_error(rv);

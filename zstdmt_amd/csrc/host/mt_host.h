@@ -1,6 +1,9 @@
 /*
- * mt_host.h -- small helpers shared by the host engines (lz4mt_engine.c, zstdmt_engine.c):
- * little-endian reads and a device buffer + pinned mirror pair that only ever grows.
+ * mt_host.h -- small helpers shared by the host engines (the texts mt_compress.inc, mt_records12.inc and
+ * mt16_engine.inc, instantiated by lz4mt_engine.c, zstdmt_engine.c, brotlimt_engine.c and snappymt_engine.c):
+ * batch sizes, the devices of a context and how its batch slots are dealt out to them, a device buffer +
+ * pinned mirror pair that only ever grows, the arrays that describe a batch of records to the decode kernels,
+ * the 12-byte record header and the error strings the four libraries have in common.
  * Plain C over include/gpumt.h; no HIP header.
  */
 #ifndef ZMT_MT_HOST_H
@@ -12,6 +15,7 @@
 #include <string.h>
 
 #include "gpumt.h"
+#include "mt_le.h"
 
 /*
  * Device batches.  The kernels are latency-bound per chunk (a wave per chunk / per record), so a
@@ -54,15 +58,6 @@ static inline size_t zmt_batch_bytes_for(size_t unit)
 	if (want > ((size_t)1 << 30))
 		want = (size_t)1 << 30;
 	return want > base ? want : base;
-}
-
-static inline uint32_t rd32(const uint8_t *p)
-{
-	return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-}
-static inline uint64_t rd64(const uint8_t *p)
-{
-	return (uint64_t)rd32(p) | (uint64_t)rd32(p + 4) << 32;
 }
 
 /*
@@ -190,6 +185,76 @@ static inline void dbuf_free(gpumt_ctx *g, dbuf *b)
 	memset(b, 0, sizeof *b);
 }
 
-/* =================================================================== compression ============ */
+/* the four buffers of a batch slot */
+static inline void dbuf_free4(gpumt_ctx *g, dbuf *a, dbuf *b, dbuf *c, dbuf *d)
+{
+	dbuf_free(g, a);
+	dbuf_free(g, b);
+	dbuf_free(g, c);
+	dbuf_free(g, d);
+}
+/* grow b to `bytes`, keeping its first `keep` pinned bytes (a record larger than what is left of the slot; nothing is in
+ * flight in it).  On failure b is as it was: freeCtx releases it. */
+static inline int dbuf_grow_keep(gpumt_ctx *g, dbuf *b, size_t keep, size_t bytes)
+{
+	dbuf old = *b;
+	memset(b, 0, sizeof *b);
+	if (dbuf_want(g, b, bytes, 1, 1)) {
+		dbuf_free(g, b);
+		*b = old;
+		return -1;
+	}
+	memcpy(b->h, old.h, keep);
+	dbuf_free(g, &old);
+	return 0;
+}
+
+/* a launched batch ends with the slot's completion mark on `stream`; the results are in pinned memory once it is waited for */
+static inline int mt_slot_mark(const mt_gpus *m, int slot, int stream)
+{
+	return gpumt_mark(mt_gpu_of(m, slot), mt_mark_of(m, slot), stream);
+}
+static inline int mt_slot_wait(const mt_gpus *m, int slot)
+{
+	return gpumt_mark_sync(mt_gpu_of(m, slot), mt_mark_of(m, slot));
+}
+
+/*
+ * What the decode kernels are told about a batch, one `meta` buffer per slot (capacity BATCH_MAXREC records):
+ * rec_off u64[n] | out_off u64[n+1] | rec_len u32[n] | out_len u32[n].  dev = 0: the pinned mirror, 1: the device copy.
+ */
+#define D_META_BYTES(n) ((n) * 8 + ((n) + 1) * 8 + (n) * 4 + (n) * 4 + 64)
+static inline uint64_t *m_rec_off(const dbuf *meta, int dev) { return (uint64_t *)(dev ? meta->d : meta->h); }
+static inline uint64_t *m_out_off(const dbuf *meta, int dev) { return m_rec_off(meta, dev) + BATCH_MAXREC; }
+static inline uint32_t *m_rec_len(const dbuf *meta, int dev) { return (uint32_t *)(m_out_off(meta, dev) + BATCH_MAXREC + 1); }
+static inline uint32_t *m_out_len(const dbuf *meta, int dev) { return m_rec_len(meta, dev) + BATCH_MAXREC; }
+
+/* the 12-byte header of an lz4-mt / zstd-mt record: skippable-frame magic, size field 4, payload bytes */
+#define MT_MAGIC_SKIPPABLE 0x184D2A50U
+static inline void mt_rec12_header(uint8_t *rec, uint32_t csize)
+{
+	rec[0] = 0x50; rec[1] = 0x2A; rec[2] = 0x4D; rec[3] = 0x18;
+	rec[4] = 4; rec[5] = rec[6] = rec[7] = 0;
+	rec[8] = (uint8_t)csize; rec[9] = (uint8_t)(csize >> 8);
+	rec[10] = (uint8_t)(csize >> 16); rec[11] = (uint8_t)(csize >> 24);
+}
+
+/* the error strings the four libraries share (lib/lz4-mt_common.c, lib/zstd-mt_common.c:40-61, lib/brotli-mt_common.c:37-57),
+ * in the order of LZ4MT_ErrorCode; NULL past them.  Which codes have a string, and what the others get, is per library. */
+static inline const char *mt_error_name(size_t idx)
+{
+	static const char *const names[] = {
+		"No error detected",
+		"Allocation error : not enough memory",
+		"Read failure",
+		"Write failure",
+		"Malformed input",
+		"Could not compress frame at once",
+		"Could not decompress frame at once",
+		"Compression parameter is out of bound",
+		"Compression library reports failure",
+	};
+	return idx < sizeof names / sizeof names[0] ? names[idx] : NULL;
+}
 
 #endif
