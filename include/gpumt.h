@@ -12,6 +12,7 @@
  *   gpumt_lz4_compact          replaces  pt_write ordering      @ lib/lz4-mt_compress.c:178-205 (F4)
  *   gpumt_lz4_decompress_batch replaces  LZ4F_decompress        @ lib/lz4-mt_decompress.c:349-362 (C3)
  *                                        + size probe           @ lib/lz4-mt_decompress.c:329-334 (F10)
+ *   gpumt_lz4_decompress_blocks replaces the streaming LZ4F_decompress @ lib/lz4-mt_decompress.c:391-483 (plain .lz4)
  *
  * Plain C types only: opaque handle, device pointers as void*, sizes as integers.  Nothing here
  * falls back to the CPU: every entry point returns GPUMT_E_NODEVICE/E_HIP when the HIP runtime or
@@ -182,6 +183,74 @@ int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream
 			       const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
 			       void *d_out, size_t out_bytes, const uint64_t *d_out_off,
 			       uint32_t *d_out_len, uint32_t *d_status, int stream);
+
+/*
+ * Block-level LZ4 decode: what the plain .lz4 path of LZ4MT_decompressDCtx uses in place of one record per frame
+ * (replaces the streaming LZ4F_decompress of st_decompress, lib/lz4-mt_decompress.c:391-483).  The caller walks the
+ * frame and block headers and passes a table of blocks and a list of runs; one wave decodes a run, its blocks back to
+ * back from d_out + out_off, at most out_cap bytes.
+ *   independent-block frame: every block is its own run, low = out_off, out_cap = what the block can decode to
+ *                            (min(blkmax, 255 x src_len), or src_len when stored); the slots are packed afterwards
+ *                            (gpumt_lz4_pack_runs) unless every one came out full
+ *   linked-block frame:      one run holds the frame's blocks of this batch; low reaches back over the history (the
+ *                            last min(64 KiB, bytes so far) of the frame's output) that the caller copied in front
+ *                            of out_off, so out_off - low <= 65536
+ * d_block_len[b] receives block b's decoded length, d_run_len[r] the run's, d_status[r] GPUMT_ST_OK, GPUMT_ST_BAD_BLOCK
+ * (malformed block, block above blkmax or above the room left; liblz4's end-of-block rules are measured from blkmax),
+ * GPUMT_ST_BAD_CHECKSUM (block checksum) or GPUMT_ST_BAD_RECORD (a table entry that leaves stream_bytes / out_bytes:
+ * the tables are device memory, the kernel checks them).  After an error the run's later blocks are not decoded.
+ * Frame header, end mark, content size and content checksum are the caller's (gpumt_xxh32_carry).  No d_stream slack.
+ */
+#define GPUMT_LZ4B_STORED 1u   /* the block body is the content */
+#define GPUMT_LZ4B_CHECKSUM 2u /* `checksum` is the XXH32 of the block body */
+typedef struct {
+	uint64_t src_off; /* block body in d_stream */
+	uint32_t src_len;
+	uint32_t flags;
+	uint32_t blkmax;  /* the frame's block maximum, 64 KiB .. 4 MiB */
+	uint32_t checksum;
+} gpumt_lz4_block;
+typedef struct {
+	uint64_t low;     /* lowest byte of d_out a match of this run may read */
+	uint64_t out_off;
+	uint32_t out_cap; /* at most 0xFFFE0000: positions inside a run are 32 bits */
+	uint32_t first, count; /* blocks [first, first + count) */
+	uint32_t reserved;
+} gpumt_lz4_run;
+#define GPUMT_LZ4_BLOCKS_MAX 0x00FFFFFFu
+int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
+				void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
+				uint32_t *d_status, int stream);
+/* Ordered concatenation of what the runs decoded: d_pack_off[0..nrun] = exclusive scan of d_run_len and run r's bytes
+ * moved from d_out + out_off to d_packed + d_pack_off[r] (d_packed_bytes: its size; must not overlap d_out). */
+int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
+			const uint32_t *d_run_len, size_t nrun, void *d_packed, size_t packed_bytes,
+			uint64_t *d_pack_off, int stream);
+
+/*
+ * XXH32 (seed 0) with carried state: job j continues a hash over d_base + off, len bytes.  GPUMT_XXH_RESET starts a new
+ * hash, otherwise the state in slot GPUMT_XXH_IN of d_states (2 x GPUMT_XXH32_STATE_WORDS words of device memory: four
+ * accumulators, up to 15 pending bytes, the total length) is continued; GPUMT_XXH_FINAL writes the digest to d_digest[j]
+ * and, with GPUMT_XXH_VERIFY, GPUMT_ST_OK / GPUMT_ST_BAD_CHECKSUM against `expect` to d_verdict[j]; without it the
+ * state goes to slot GPUMT_XXH_OUT.  One wave per job, the jobs of a call side by side: a call holds at most one job that
+ * reads a state and one that leaves one, and they name different slots.  A job outside base_bytes: GPUMT_ST_BAD_RECORD.
+ */
+#define GPUMT_XXH32_STATE_WORDS 12
+#define GPUMT_XXH_RESET 1u
+#define GPUMT_XXH_FINAL 2u
+#define GPUMT_XXH_VERIFY 4u
+#define GPUMT_XXH_IN(slot) ((uint32_t)((slot) & 1) << 8)
+#define GPUMT_XXH_OUT(slot) ((uint32_t)((slot) & 1) << 9)
+typedef struct {
+	uint64_t off;
+	uint32_t len;
+	uint32_t flags;
+	uint32_t expect;
+	uint32_t reserved;
+} gpumt_xxh32_job;
+int gpumt_xxh32_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
+		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int stream);
 
 /* ---- zstd-mt records (12-byte skippable header + one zstd frame, lib/zstd-mt_compress.c:296-302) ----
  *

@@ -38,6 +38,11 @@ __global__ void zmt_lz4_enc3_u32_kernel(const u8 *, u64, u32, u32, u32, u8 *, u6
 					unsigned long long *);
 __global__ void zmt_lz4_dec_serial(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *,
 				   u32 *, u32 *, u32 *, u32 *, u32);
+__global__ void zmt_lz4_dec_blocks_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u8 *,
+					  u64, u32 *, u32 *, u32 *);
+__global__ void zmt_lz4_gather_runs_kernel(const u8 *, u64, const gpumt_lz4_run *, const u32 *, const u64 *, u32, u8 *,
+					   u64);
+__global__ void zmt_xxh32_carry_kernel(const u8 *, u64, const gpumt_xxh32_job *, u32, u32 *, u32 *, u32 *);
 __global__ void zmt_dec_nblk_kernel(const u32 *, u32, u32 *);
 __global__ void zmt_dec_frames_kernel(const u8 *, const u64 *, const u32 *, u32, const u32 *,
 				      const u64 *, u64 *, u32 *, u32 *, u32 *, u32 *, u32 *, u32 *);
@@ -979,6 +984,64 @@ int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream
 	hipLaunchKernelGGL(zmt_xxh32_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), dim3(256), 0,
 			   h->st[s], (const u8 *)d_out, d_out_off, d_out_len, n, (u32 *)NULL,
 			   (const u32 *)ce, (const u32 *)cv, d_status);
+	PROF1(12);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
+				void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
+				uint32_t *d_status, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_stream || !d_blocks || !d_runs || !d_out || !d_block_len || !d_run_len || !d_status ||
+	    nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	PROF0(11);
+	hipLaunchKernelGGL(zmt_lz4_dec_blocks_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out, (u64)out_bytes,
+			   d_block_len, d_run_len, d_status);
+	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
+			const uint32_t *d_run_len, size_t nrun, void *d_packed, size_t packed_bytes,
+			uint64_t *d_pack_off, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_out || !d_runs || !d_run_len || !d_packed || !d_pack_off || nrun == 0 ||
+	    nrun > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	/* the two areas must not overlap: the runs are moved side by side */
+	if ((const u8 *)d_packed < (const u8 *)d_out + out_bytes && (const u8 *)d_out < (const u8 *)d_packed + packed_bytes)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	PROF0(10);
+	hipLaunchKernelGGL(zmt_scan_kernel, dim3(1), dim3(1024), 0, h->st[s], d_run_len, (u32)nrun, d_pack_off);
+	hipLaunchKernelGGL(zmt_lz4_gather_runs_kernel, dim3((unsigned)nrun), dim3(256), 0, h->st[s], (const u8 *)d_out,
+			   (u64)out_bytes, d_runs, d_run_len, (const u64 *)d_pack_off, (u32)nrun, (u8 *)d_packed,
+			   (u64)packed_bytes);
+	PROF1(10);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+int gpumt_xxh32_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
+		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_base || !d_jobs || !d_states || !d_digest || !d_verdict || njobs > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	if (!njobs)
+		return GPUMT_OK;
+	PROF0(12);
+	hipLaunchKernelGGL(zmt_xxh32_carry_kernel, dim3((unsigned)njobs), dim3(64), 0, h->st[s], (const u8 *)d_base,
+			   (u64)base_bytes, d_jobs, (u32)njobs, d_states, d_digest, d_verdict);
 	PROF1(12);
 	CK(hipGetLastError());
 	return GPUMT_OK;

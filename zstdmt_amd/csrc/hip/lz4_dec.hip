@@ -215,3 +215,166 @@ done:
 	if (lane == 0)
 		status[rec] = st;
 }
+
+/*
+ * Block-level entry (gpumt_lz4_decompress_blocks): the plain .lz4 path of the host engine walks the frame and block
+ * headers itself and hands over a table of blocks and a list of runs.  A run is a group of consecutive blocks that one
+ * wave decodes back to back from out_base + out_off: one block of an independent-block frame (low = out_off), or the
+ * blocks a linked-block frame has in this batch (low reaches back over the history the caller placed in front, at
+ * most 64 KiB: LZ4 offsets are 16 bits).  Order inside a run comes from the run being one wave; no run looks at
+ * another's memory.  The table entries live in device memory, so they are checked here against the sizes the host
+ * passed: an entry that leaves the stream or the output is ST_BAD_RECORD and nothing of it is touched.
+ * Verdicts as zmt_lz4_dec_serial: ST_BAD_BLOCK (malformed, above the block maximum, no room), ST_BAD_CHECKSUM.
+ */
+struct Lz4Block { /* == gpumt_lz4_block */
+	u64 src_off;
+	u32 src_len, flags, blkmax, checksum;
+};
+struct Lz4Run { /* == gpumt_lz4_run */
+	u64 low, out_off;
+	u32 out_cap, first, count, reserved;
+};
+#define LZ4B_STORED 1u
+#define LZ4B_CHECKSUM 2u
+
+extern "C" __global__ void __launch_bounds__(64)
+zmt_lz4_dec_blocks_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const Lz4Block *__restrict__ blocks, u32 nblk,
+			  const Lz4Run *__restrict__ runs, u32 nrun, u8 *out_base, u64 out_bytes,
+			  u32 *__restrict__ blk_len, u32 *__restrict__ run_len, u32 *__restrict__ status)
+{
+	const u32 r = blockIdx.x;
+	const int lane = wv_lane();
+	if (r >= nrun)
+		return;
+	const Lz4Run R = runs[r];
+	u32 st = ST_OK, opos = 0, start = 0;
+	if (R.first > nblk || R.count > nblk - R.first || R.low > R.out_off || R.out_off > out_bytes ||
+	    R.out_cap > out_bytes - R.out_off || R.out_off - R.low > 0x10000u || R.out_cap > 0xFFFE0000u) {
+		st = ST_BAD_RECORD;
+		goto done;
+	}
+	{
+		u8 *out = out_base + R.low;
+		const u32 end = wv_readfirst((u32)(R.out_off - R.low) + R.out_cap);
+		start = opos = wv_readfirst((u32)(R.out_off - R.low));
+		for (u32 b = R.first; b < R.first + R.count; b++) {
+			const Lz4Block B = blocks[b];
+			const u32 bsz = wv_readfirst(B.src_len), bm = wv_readfirst(B.blkmax);
+			const u8 *src = stream + B.src_off;
+			if (B.src_off > stream_bytes || bsz > stream_bytes - B.src_off || bm < 65536u || bm > (4u << 20)) {
+				st = ST_BAD_RECORD;
+				break;
+			}
+			if (bsz > bm) {
+				st = ST_BAD_BLOCK;
+				break;
+			}
+			if ((B.flags & LZ4B_CHECKSUM) && wave_xxh32(src, bsz, lane) != wv_readfirst(B.checksum)) {
+				st = ST_BAD_CHECKSUM; /* LZ4F_ERROR_blockChecksum_invalid */
+				break;
+			}
+			u32 np;
+			if (B.flags & LZ4B_STORED) {
+				if (end - opos < bsz) {
+					st = ST_BAD_BLOCK;
+					break;
+				}
+				wave_copy(out + opos, src, bsz, lane);
+				np = opos + bsz;
+			} else {
+				const u32 room = end - opos < bm ? end - opos : bm;
+				np = decode_block_serial(src, bsz, out, opos, 0, opos + room, bm, lane);
+				if (np == 0xFFFFFFFFu) {
+					st = ST_BAD_BLOCK;
+					break;
+				}
+			}
+			if (lane == 0)
+				blk_len[b] = np - opos;
+			opos = np;
+		}
+	}
+done:
+	if (lane == 0) {
+		run_len[r] = opos - start;
+		status[r] = st;
+	}
+}
+
+/* run r's decoded bytes (out_base + out_off, run_len[r] of them) -> dst + off[r]: the pack of the slots of
+ * independent blocks that decoded to less than their capacity (off = zmt_scan_kernel over run_len); the pattern of
+ * zmt_compact_kernel with a slot table in place of a stride */
+extern "C" __global__ void __launch_bounds__(256)
+zmt_lz4_gather_runs_kernel(const u8 *__restrict__ out_base, u64 out_bytes, const Lz4Run *__restrict__ runs,
+			   const u32 *__restrict__ run_len, const u64 *__restrict__ off, u32 nrun, u8 *__restrict__ dst,
+			   u64 dst_bytes)
+{
+	const u32 r = blockIdx.x;
+	if (r >= nrun)
+		return;
+	const u64 so = runs[r].out_off, dofs = off[r];
+	const u32 n = run_len[r];
+	if (so > out_bytes || n > out_bytes - so || dofs > dst_bytes || n > dst_bytes - dofs)
+		return;
+	const u8 *s = out_base + so;
+	u8 *d = dst + dofs;
+	for (u32 i = threadIdx.x * 4; i + 4 <= n; i += 1024)
+		st32u(d + i, ld32u(s + i));
+	if (threadIdx.x < (n & 3))
+		d[(n & ~3u) + threadIdx.x] = s[(n & ~3u) + threadIdx.x];
+}
+
+#ifdef ZMT_EMU
+/*
+ * TEST HARNESS ONLY (tests/emu compiles this file as host C++): the two device calls above over the fiber emulator,
+ * with the shapes of include/gpumt.h, so that the host engine's plain .lz4 path runs on the CPU.  Synchronous, host
+ * pointers stand in for device pointers; the same argument checks as gpumt.hip.  Never part of the product.
+ */
+#include "../../../include/gpumt.h"
+extern "C" {
+void zmt_scan_kernel(const u32 *, u32, u64 *);
+
+void emu_lz4_decompress_blocks(const u8 *stream, u64 stream_bytes, const void *blocks, u32 nblk, const void *runs,
+			       u32 nrun, u8 *out, u64 out_bytes, u32 *blk_len, u32 *run_len, u32 *status)
+{
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_lz4_dec_blocks_kernel(stream, stream_bytes, (const Lz4Block *)blocks, nblk, (const Lz4Run *)runs, nrun, out,
+					  out_bytes, blk_len, run_len, status);
+	});
+}
+
+void emu_lz4_pack_runs(const u8 *out, u64 out_bytes, const void *runs, const u32 *run_len, u32 nrun, u8 *packed,
+		       u64 packed_bytes, u64 *pack_off)
+{
+	emu::launch(emu::dim3{1, 1, 1}, emu::dim3{1024, 1, 1}, [=]() { zmt_scan_kernel(run_len, nrun, pack_off); });
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{256, 1, 1}, [=]() {
+		zmt_lz4_gather_runs_kernel(out, out_bytes, (const Lz4Run *)runs, run_len, pack_off, nrun, packed, packed_bytes);
+	});
+}
+
+int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const gpumt_lz4_block *d_blocks,
+				size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun, void *d_out, size_t out_bytes,
+				uint32_t *d_block_len, uint32_t *d_run_len, uint32_t *d_status, int s)
+{
+	static_assert(sizeof(gpumt_lz4_block) == sizeof(Lz4Block) && sizeof(gpumt_lz4_run) == sizeof(Lz4Run), "table layout");
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_stream || !d_blocks || !d_runs || !d_out || !d_block_len || !d_run_len ||
+	    !d_status || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	emu_lz4_decompress_blocks((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
+				  out_bytes, d_block_len, d_run_len, d_status);
+	return GPUMT_OK;
+}
+
+int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
+			const uint32_t *d_run_len, size_t nrun, void *d_packed, size_t packed_bytes, uint64_t *d_pack_off, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_out || !d_runs || !d_run_len || !d_packed || !d_pack_off || nrun == 0 ||
+	    nrun > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if ((const u8 *)d_packed < (const u8 *)d_out + out_bytes && (const u8 *)d_out < (const u8 *)d_packed + packed_bytes)
+		return GPUMT_E_ARG;
+	emu_lz4_pack_runs((const u8 *)d_out, out_bytes, d_runs, d_run_len, (u32)nrun, (u8 *)d_packed, packed_bytes, d_pack_off);
+	return GPUMT_OK;
+}
+}
+#endif

@@ -12,8 +12,8 @@
  * kernel streams, while another is read into or written out).  Callback-visible behaviour follows the reference: compress issues one fn_read of
  * exactly `inputsize` bytes per chunk and one fn_write per record, in input order; decompress
  * reads 4, then 8|12 header bytes and the payload per record, and writes one chunk per call.
- * The compress half is mt_compress.inc, the record pipeline and the plain-stream path are mt_records12.inc (both shared
- * with zstdmt_engine.c); this file holds what is lz4-mt's own: the error strings, the parameters and hooks of the two
+ * The compress half is mt_compress.inc, the record pipeline is mt_records12.inc (both shared with zstdmt_engine.c), the
+ * plain .lz4 path (block-parallel, frames of any size) is mt_lz4_plain.inc; this file holds what is lz4-mt's own: the error strings, the parameters and hooks of the two
  * texts and the 4-byte sniff of LZ4MT_decompressDCtx.
  * This file is plain C and never includes a HIP header.
  */
@@ -74,14 +74,11 @@ const char *LZ4MT_getErrorString(size_t code)
 #define MT_D12_STATUS_PRESET 0
 #define MT_DECOMPRESS_BATCH gpumt_lz4_decompress_batch
 #define MT_FRAME_MAGIC LZ4FMT_MAGICNUMBER
-#define MT_PLAIN_VARIANT "lz4_dec"
 #define MT_PLAIN_REQUEST(ctx) ((size_t)(ctx)->inputsize) /* inputsize requests, lz4-mt_decompress.c:462-476 */
 #define MT_PLAIN_FIRST_FILLS 0
 #define MT_PLAIN_PIECE(ctx) ((ctx)->inputsize < 65536 ? (size_t)65536 : (size_t)(ctx)->inputsize)
 #define MT_PLAIN_ENTER(ctx, nfirst) ((ctx)->insize = (nfirst), (ctx)->outsize = 0)
 #define MT_PLAIN_COUNT_FAILED_WRITE 1
-
-#include "mt_frame_extent.h"
 
 /* output size = LE64 at payload+6 (lz4-mt_decompress.c:333-334); frames that carry no
  * content size (only the empty frame is written that way) decode to nothing */
@@ -104,18 +101,13 @@ static size_t d12_status_error(uint32_t st)
 	return ERROR(compression_library);
 }
 
-/* plain .lz4 streams: typically 4 MiB linked blocks and no content size; decoded by the frame-serial kernel, a frame
- * that does not state its content size gets blocks x block-maximum as capacity */
-static size_t plain_frame_extent(const uint8_t *p, size_t n, uint64_t *bound)
-{
-	int supported = 0;
-	const size_t flen = lz4_frame_extent(p, n, bound, &supported);
-	return flen && !supported ? EXTENT_INVALID : flen;
-}
-
+/* plain .lz4 streams (typically 4 MiB blocks and no content size) are decoded block by block, mt_lz4_plain.inc;
+ * mt_records12.inc's frame-per-record plain path is left out */
+#define MT_PLAIN_BLOCKS 1
 static size_t plain_bad_frame(void) { return ERROR(compression_library); }
 
 #include "mt_records12.inc"
+#include "mt_lz4_plain.inc"
 
 size_t LZ4MT_decompressDCtx(LZ4MT_DCtx *ctx, LZ4MT_RdWr_t *rdwr)
 {
@@ -138,7 +130,7 @@ size_t LZ4MT_decompressDCtx(LZ4MT_DCtx *ctx, LZ4MT_RdWr_t *rdwr)
 		if (rd32(magic) != LZ4FMT_MAGICNUMBER)
 			return ERROR(data_error);
 		/* plain .lz4 stream: the reference decodes it single-threaded (st_decompress, :391-483) */
-		return plain_decompress(ctx, rdwr, magic, 4, 0);
+		return lz4_plain_decompress(ctx, rdwr, magic, 4);
 	}
 	ctx->have_hdr = 0;
 	ctx->first_hdr = 1;

@@ -13,6 +13,8 @@
  *                               visits some of them)
  *   MT_DECOMPRESS_BATCH         gpumt_*_decompress_batch
  *   MT_FRAME_MAGIC              first four bytes of a frame the plain path takes
+ *   MT_PLAIN_BLOCKS             (optional) the including file brings its own plain path (lz4-mt: mt_lz4_plain.inc, block by
+ *                               block); plain_decompress and its two hooks are left out, plain_write stays
  *   MT_PLAIN_VARIANT            (optional) kernel family whose variant 1 the plain path forces around its batches
  *   MT_PLAIN_REQUEST(ctx)       bytes per fn_read of the plain path
  *   MT_PLAIN_FIRST_FILLS        1: the first request is shortened by the bytes that came with the sniff
@@ -328,6 +330,7 @@ static size_t plain_write(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *p, siz
 	return 0;
 }
 
+#ifndef MT_PLAIN_BLOCKS
 /* first[0..nfirst) came with the sniff; at_eof: the sniff already hit the end of the input */
 static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *first, size_t nfirst, int at_eof)
 {
@@ -504,3 +507,4 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 	free(raw);
 	return err;
 }
+#endif /* MT_PLAIN_BLOCKS */

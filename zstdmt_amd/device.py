@@ -13,6 +13,15 @@ ST_NAMES = {0: "ok", 1: "bad_record", 2: "bad_frame", 3: "bad_block", 4: "size_m
             5: "bad_checksum", 6: "trailing", 7: "unsupported"}
 
 
+# gpumt_lz4_block / gpumt_lz4_run / gpumt_xxh32_job (include/gpumt.h) as numpy record types
+LZ4_BLOCK = np.dtype([("src_off", "<u8"), ("src_len", "<u4"), ("flags", "<u4"), ("blkmax", "<u4"), ("checksum", "<u4")])
+LZ4_RUN = np.dtype([("low", "<u8"), ("out_off", "<u8"), ("out_cap", "<u4"), ("first", "<u4"), ("count", "<u4"),
+                    ("reserved", "<u4")])
+XXH32_JOB = np.dtype([("off", "<u8"), ("len", "<u4"), ("flags", "<u4"), ("expect", "<u4"), ("reserved", "<u4")])
+LZ4B_STORED, LZ4B_CHECKSUM = 1, 2
+XXH_RESET, XXH_FINAL, XXH_VERIFY = 1, 2, 4
+
+
 class DevBuf:
     __slots__ = ("ptr", "nbytes", "eng")
 
@@ -176,6 +185,65 @@ class Engine:
                                                    d_rec_off.ptr, d_rec_len.ptr, nrec, d_out.ptr,
                                                    int(out_bytes), d_out_off.ptr, d_out_len.ptr,
                                                    d_status.ptr, stream), "lz4_decompress_batch")
+
+    def lz4_decompress_blocks(self, stream: bytes, blocks, runs, out_bytes, history=b"", pack=False):
+        """gpumt_lz4_decompress_blocks over host bytes: `blocks` / `runs` are LZ4_BLOCK / LZ4_RUN arrays, `history` is
+        placed at the start of the output (what a linked run reads behind its `low`).  -> (output area bytes,
+        block_len[nblk], run_len[nrun], status[nrun]); with pack=True the output is what gpumt_lz4_pack_runs made of
+        the runs, in order."""
+        blocks = np.ascontiguousarray(blocks, LZ4_BLOCK)
+        runs = np.ascontiguousarray(runs, LZ4_RUN)
+        nblk, nrun = len(blocks), len(runs)
+        area = np.full(int(out_bytes) + 64, 0xCC, np.uint8)
+        area[:len(history)] = np.frombuffer(history, np.uint8)
+        d_stream = self.upload(stream, slack=0) if stream else self.alloc(64)
+        d_blk, d_run, d_out = self.upload(blocks.view(np.uint8)), self.upload(runs.view(np.uint8)), self.upload(area, slack=0)
+        d_bl, d_rl, d_st = self.upload(np.zeros(nblk + 1, np.uint32)), self.alloc(nrun * 4), self.alloc(nrun * 4)
+        d_pk, d_po = self.alloc(int(out_bytes) + 64), self.alloc((nrun + 1) * 8)
+        try:
+            self._ck(self.L.gpumt_lz4_decompress_blocks(self.h, d_stream.ptr, len(stream), d_blk.ptr, nblk, d_run.ptr, nrun,
+                                                        d_out.ptr, int(out_bytes), d_bl.ptr, d_rl.ptr, d_st.ptr, 0),
+                     "lz4_decompress_blocks")
+            status = self.download(d_st, nrun * 4, np.uint32)
+            run_len = self.download(d_rl, nrun * 4, np.uint32)
+            blk_len = self.download(d_bl, nblk * 4, np.uint32)
+            raw = self.download(d_out, int(out_bytes) + 64)
+            assert (raw[int(out_bytes):] == 0xCC).all(), "decoder wrote past the end of its output"
+            out = raw[:int(out_bytes)].tobytes()
+            if pack:
+                self._ck(self.L.gpumt_lz4_pack_runs(self.h, d_out.ptr, int(out_bytes), d_run.ptr, d_rl.ptr, nrun, d_pk.ptr,
+                                                    int(out_bytes), d_po.ptr, 0), "lz4_pack_runs")
+                total = int(self.download(d_po, (nrun + 1) * 8, np.uint64)[nrun])
+                out = self.download(d_pk, total).tobytes()
+        finally:
+            for b in (d_stream, d_blk, d_run, d_out, d_bl, d_rl, d_st, d_pk, d_po):
+                b.free()
+        return out, blk_len, run_len, status
+
+    def xxh32_carry(self, data: bytes, pieces):
+        """XXH32 of `data` continued over `pieces` (lengths that add up to len(data)), one gpumt_xxh32_carry call per piece
+        with the state carried on the device -> digest"""
+        assert sum(pieces) == len(data) and pieces
+        d_data = self.upload(data) if data else self.alloc(64)
+        d_states, d_dig, d_ver, d_job = self.alloc(96), self.alloc(4), self.alloc(4), self.alloc(XXH32_JOB.itemsize)
+        try:
+            at, xs = 0, 0
+            for i, n in enumerate(pieces):
+                last = i == len(pieces) - 1
+                job = np.zeros(1, XXH32_JOB)
+                job["off"], job["len"] = at, n
+                job["flags"] = (XXH_RESET if i == 0 else xs << 8) | (XXH_FINAL if last else (xs ^ 1) << 9)
+                if not last:
+                    xs ^= 1
+                self._ck(self.L.gpumt_memcpy_h2d(self.h, d_job.ptr, job.ctypes.data, job.nbytes, 0), "h2d")
+                self.sync(0)
+                self._ck(self.L.gpumt_xxh32_carry(self.h, d_data.ptr, len(data), d_job.ptr, 1, d_states.ptr, d_dig.ptr,
+                                                  d_ver.ptr, 0), "xxh32_carry")
+                at += n
+            return int(self.download(d_dig, 4, np.uint32)[0])
+        finally:
+            for b in (d_data, d_states, d_dig, d_ver, d_job):
+                b.free()
 
     def zstd_slot_stride(self, chunk):
         return int(self.L.gpumt_zstd_slot_stride(chunk))
