@@ -13,6 +13,7 @@
  *   gpumt_lz4_decompress_batch replaces  LZ4F_decompress        @ lib/lz4-mt_decompress.c:349-362 (C3)
  *                                        + size probe           @ lib/lz4-mt_decompress.c:329-334 (F10)
  *   gpumt_lz4_decompress_blocks replaces the streaming LZ4F_decompress @ lib/lz4-mt_decompress.c:391-483 (plain .lz4)
+ *   gpumt_zstd_decompress_blocks replaces the streaming ZSTD_decompressStream @ lib/zstd-mt_decompress.c:552-687 (plain .zst)
  *
  * Plain C types only: opaque handle, device pointers as void*, sizes as integers.  Nothing here
  * falls back to the CPU: every entry point returns GPUMT_E_NODEVICE/E_HIP when the HIP runtime or
@@ -302,6 +303,59 @@ int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t strea
 				const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
 				void *d_out, size_t out_bytes, const uint64_t *d_out_off,
 				uint32_t *d_out_len, uint32_t *d_status, int stream);
+
+/*
+ * Block-level zstd decode: what the plain .zst path of ZSTDCB_decompressDCtx uses in place of one record per frame
+ * (replaces the streaming ZSTD_decompressStream of st_decompress, lib/zstd-mt_decompress.c:552-687).  The caller walks the
+ * frame and block headers and passes a table of blocks and a list of runs; a run is the consecutive blocks of one frame
+ * that a call holds, and one wave decodes it, block after block, to d_out + out_off, at most out_cap bytes.
+ *   a whole frame:          one run with GPUMT_ZRUN_FIRST | GPUMT_ZRUN_LAST; runs of different frames decode side by side
+ *   a frame over several calls: its runs go one per call, in order.  What a later block may refer to -- the three repeat
+ *                           offsets, the Huffman table (treeless literals), the LL / OF / ML tables (Repeat_Mode) -- is
+ *                           left in slot `carry` (0 or 1) of d_carry (2 x GPUMT_ZSTD_CARRY_BYTES of device memory) unless
+ *                           the run is LAST, and taken from there unless it is FIRST.  The caller places the last `hist`
+ *                           bytes of the frame's earlier output (min(bytes so far, window)) directly in front of out_off:
+ *                           a match may reach back that far and no further.  The runs of one call that name a carry slot
+ *                           belong to different frames when they name different slots.
+ * d_run_len[r] receives the bytes run r decoded, d_status[r] GPUMT_ST_OK, GPUMT_ST_BAD_BLOCK (malformed block, block
+ * above block_max or above the room left, a match that reaches in front of the history, a treeless or Repeat_Mode block
+ * whose table neither the run nor the carry holds, a run behind one that failed) or GPUMT_ST_BAD_RECORD (a table entry
+ * that leaves stream_bytes / out_bytes, or whose src_len is not the length its block header states: the tables are device
+ * memory, the kernel checks them).  Frame header, Frame_Content_Size and the content checksum are the caller's
+ * (gpumt_xxh64_carry).  Same d_stream slack rule as gpumt_zstd_decompress_batch; stream_bytes below 4 GiB.
+ * Internal scratch: GPUMT_ZSTD_RUN_SCRATCH bytes per run.
+ */
+#define GPUMT_ZRUN_FIRST 1u
+#define GPUMT_ZRUN_LAST 2u
+#define GPUMT_ZSTD_CARRY_BYTES 9280u
+#define GPUMT_ZSTD_RUN_SCRATCH 131328u
+typedef struct {
+	uint64_t src_off;   /* the block's 3-byte header in d_stream */
+	uint32_t src_len;   /* header + body (4 for an RLE block) */
+	uint32_t block_max; /* min(the frame's window, 128 KiB) */
+} gpumt_zstd_block;
+typedef struct {
+	uint64_t out_off;
+	uint32_t out_cap;      /* hist + out_cap at most 0xFFFE0000: positions inside a run are 32 bits */
+	uint32_t hist;         /* bytes of the frame's earlier output in front of out_off */
+	uint32_t first, count; /* blocks [first, first + count) */
+	uint32_t flags;        /* GPUMT_ZRUN_* */
+	uint32_t carry;        /* slot of d_carry, 0 or 1 */
+} gpumt_zstd_run;
+int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				 const gpumt_zstd_block *d_blocks, size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun,
+				 void *d_out, size_t out_bytes, void *d_carry, uint32_t *d_run_len, uint32_t *d_status,
+				 int stream);
+
+/*
+ * XXH64 (seed 0) with carried state, the content checksum of a zstd frame decoded over several calls: gpumt_xxh32_carry's
+ * contract with the same job record and flags, a state of GPUMT_XXH64_STATE_WORDS words per slot (four 64-bit
+ * accumulators, the total length, up to 31 pending bytes), and `expect` / d_digest are the low 32 bits of the hash --
+ * what a zstd frame stores (RFC 8878 3.1.1).
+ */
+#define GPUMT_XXH64_STATE_WORDS 20
+int gpumt_xxh64_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
+		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int stream);
 
 /* ---- brotli-mt records (16-byte header + one raw brotli stream, lib/brotli-mt_compress.c:285-304) ----
  *

@@ -84,6 +84,9 @@ __global__ void zmt_zstd_dec_kernel_prof(const u8 *, u64, const u64 *, const u32
 					 u32 *, u8 *, u32 *, u32 *, u32 *, u32, unsigned long long *, u8 *, u64);
 __global__ void zmt_zstd_seq_kernel(const u8 *, u64, const u64 *, const u32 *, u32, const u64 *, const u32 *,
 				    const u32 *, u8 *, u64);
+__global__ void zmt_zstd_dec_run_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
+					u64, u8 *, u32 *, u32 *, u8 *);
+__global__ void zmt_xxh64_carry_kernel(const u8 *, u64, const gpumt_xxh32_job *, u32, u32 *, u32 *, u32 *);
 __global__ void zmt_xxh64_verify_kernel(const u8 *, const u64 *, const u32 *, u32, const u32 *, const u32 *,
 					u32 *);
 __global__ void zmt_zstd_enc_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *);
@@ -1218,6 +1221,49 @@ int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t strea
 			   h->st[s], (const u8 *)d_out, d_out_off, (const u32 *)d_out_len, (u32)nrec, (const u32 *)chk_e,
 			   (const u32 *)chk_v, d_status);
 	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				 const gpumt_zstd_block *d_blocks, size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun,
+				 void *d_out, size_t out_bytes, void *d_carry, uint32_t *d_run_len, uint32_t *d_status, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_stream || !d_blocks || !d_runs || !d_out || !d_carry || !d_run_len || !d_status ||
+	    nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX || stream_bytes > 0xFFFFFFF0u)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	/* literal scratch per run bounds a launch: slices of at most ZR_SLICE runs (512 MiB of scratch) */
+	const size_t ZR_SLICE = 4096;
+	const size_t slice = nrun < ZR_SLICE ? nrun : ZR_SLICE;
+	if (want_scratch(h, 1, s, slice * (size_t)GPUMT_ZSTD_RUN_SCRATCH))
+		return GPUMT_E_HIP;
+	PROF0(11);
+	for (size_t b = 0; b < nrun; b += slice) {
+		const size_t m = nrun - b < slice ? nrun - b : slice;
+		hipLaunchKernelGGL(zmt_zstd_dec_run_kernel, dim3((unsigned)m), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+				   (u64)stream_bytes, d_blocks, (u32)nblk, d_runs + b, (u32)m, (u8 *)d_out, (u64)out_bytes,
+				   (u8 *)d_carry, d_run_len + b, d_status + b, (u8 *)h->scratch[1][s]);
+	}
+	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+int gpumt_xxh64_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
+		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_base || !d_jobs || !d_states || !d_digest || !d_verdict || njobs > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	if (!njobs)
+		return GPUMT_OK;
+	PROF0(12);
+	hipLaunchKernelGGL(zmt_xxh64_carry_kernel, dim3((unsigned)njobs), dim3(64), 0, h->st[s], (const u8 *)d_base,
+			   (u64)base_bytes, d_jobs, (u32)njobs, d_states, d_digest, d_verdict);
+	PROF1(12);
 	CK(hipGetLastError());
 	return GPUMT_OK;
 }

@@ -54,6 +54,30 @@ static_assert(offsetof(ZLdsSmall, sq) - offsetof(ZLdsSmall, below) == 1056 &&
 
 enum { ZM_ERR = 0, ZM_A, ZM_B, ZM_C, ZM_D, ZM_E, ZM_F, ZM_G, ZM_H };
 
+/* ------------------------------------------------------------------ block runs (gpumt_zstd_decompress_blocks)
+ * A plain .zst frame larger than a batch is decoded run by run: the consecutive blocks of the frame that one batch holds,
+ * one wave per run, started at a block header.  The caller has parsed the frame header and the block headers. */
+struct ZBlock { /* == gpumt_zstd_block */
+	u64 src_off; /* the 3-byte block header in the stream */
+	u32 src_len; /* header + body */
+	u32 block_max;
+};
+struct ZRun { /* == gpumt_zstd_run */
+	u64 out_off;
+	u32 out_cap, hist, first, count, flags, carry;
+};
+#define ZR_FIRST 1u /* the frame starts here: nothing is carried in */
+#define ZR_LAST 2u  /* the frame ends here: nothing is carried out */
+/* What a later block of a frame may refer to (RFC 8878 3.1.1.3.1.1 treeless literals, 3.1.1.3.2.1 Repeat_Mode, 3.1.1.5
+ * repeat offsets), as the wave holds it when a run ends; `corrupt` fails the runs that follow a failed one. */
+struct ZCarry { /* GPUMT_ZSTD_CARRY_BYTES */
+	u32 rep[3], huf_ok, huf_log, tab_ok[3], tab_log[3], tab_pre[3], corrupt, pad;
+	u16 huf[1 << 11];
+	u32 ll[1 << 9], of[1 << 8], ml[1 << 9];
+};
+static_assert(sizeof(ZCarry) == 9280, "GPUMT_ZSTD_CARRY_BYTES in include/gpumt.h");
+#define Z_RUN_LITSLOT (Z_BLOCK_MAX + 256u) /* literal scratch per run = GPUMT_ZSTD_RUN_SCRATCH */
+
 
 /* ------------------------------------------------------------------ the kernel */
 #ifdef ZMT_EMU
@@ -81,12 +105,17 @@ static inline u32 zbad_(int line)
 		}                                                                                  \
 	} while (0)
 
-template <bool PROF, typename LDS>
+/* RUN: the same decoder started at a block header instead of a frame header (zmt_zstd_dec_run_kernel, at the end of this
+ * file): "record" rec is run rec of `runs`, its blocks are entries of `blocks`, out_len receives the run's length, and what
+ * a frame's later blocks may refer to travels in a ZCarry.  No units and no pre-pass there: one block after the other. */
+template <bool PROF, typename LDS, bool RUN = false>
 static __device__ __forceinline__ void
 zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream_bytes, const u64 *__restrict__ rec_off,
 	      const u32 *__restrict__ rec_len, u32 nrec, u8 *out_base, const u64 *__restrict__ out_off,
 	      u32 *__restrict__ out_len, u8 *__restrict__ litbuf, u32 *__restrict__ status,
-	      u32 *__restrict__ chk_expect, u32 *__restrict__ chk_valid, unsigned long long *prof, u8 *seqbuf, u64 seqcap)
+	      u32 *__restrict__ chk_expect, u32 *__restrict__ chk_valid, unsigned long long *prof, u8 *seqbuf, u64 seqcap,
+	      const ZBlock *__restrict__ blocks = nullptr, u32 nblk = 0, const ZRun *__restrict__ runs = nullptr,
+	      u64 out_bytes = 0, u8 *carry_base = nullptr)
 {
 	const int lane = wv_lane();
 	u64 pc[PROF ? 8 : 1] = {0}, tq = ZT();
@@ -99,37 +128,52 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 	const u32 rec = blockIdx.x;
 	if (rec >= nrec)
 		return;
-	if (wv_readfirst(status[rec]) != want_status)
+	/* a run (RUN) has no record and no frame header: its descriptor stands in for them.  The tables are device memory,
+	 * so they are checked here.  Positions count from the start of the history in front of the run's output: a match
+	 * may reach back that far and no further. */
+	const ZRun R = RUN ? runs[rec] : ZRun{};
+	if (RUN && (R.out_off > out_bytes || R.out_cap > out_bytes - R.out_off || R.hist > R.out_off ||
+		    (u64)R.hist + R.out_cap > 0xFFFE0000ull || R.first > nblk || R.count > nblk - R.first || R.carry > 1 ||
+		    stream_bytes > 0xFFFFFFF0ull)) {
+		if (lane == 0) {
+			out_len[rec] = 0;
+			status[rec] = ST_BAD_RECORD;
+		}
+		return;
+	}
+	ZCarry *cy = RUN ? (ZCarry *)(carry_base + (size_t)R.carry * sizeof(ZCarry)) : nullptr;
+	const u32 run_hist = R.hist, run_count = R.count, run_first = R.first, run_flags = R.flags;
+	if (!RUN && wv_readfirst(status[rec]) != want_status)
 		return; /* rejected by the probe kernel, or not this variant's record */
-	if (lane == 0)
+	if (!RUN && lane == 0)
 		chk_valid[rec] = 0;
-	const u64 roff = rec_off[rec];
-	const u32 rlen = wv_readfirst(rec_len[rec]);
+	const u64 roff = RUN ? 0 : rec_off[rec];
+	const u32 rlen = RUN ? 12u : wv_readfirst(rec_len[rec]);
 	const u8 *r = stream + roff;
-	u8 *out = out_base + out_off[rec];
-	const u32 cap = wv_readfirst(out_len[rec]);
-	u8 *lit_scratch = litbuf + (u64)rec * Z_LITSLOT;
+	u8 *out = out_base + (RUN ? R.out_off - R.hist : out_off[rec]);
+	const u32 cap = RUN ? R.hist + R.out_cap : wv_readfirst(out_len[rec]);
+	u8 *lit_scratch = litbuf + (u64)rec * (RUN ? Z_RUN_LITSLOT : Z_LITSLOT);
 	const u8 *mem_lo = stream, *mem_hi = stream + stream_bytes + 256; /* readable range */
 	u32 stc = ST_OK;
 
 	/* ---- record + frame header (RFC 8878 3.1.1) ---- */
-	if (rlen < 12 + 6 || uld32(r) != ZMT_SKIP_MAGIC || uld32(r + 4) != 4 || uld32(r + 8) != rlen - 12) {
+	if (!RUN && (rlen < 12 + 6 || uld32(r) != ZMT_SKIP_MAGIC || uld32(r + 4) != 4 || uld32(r + 8) != rlen - 12)) {
 		if (lane == 0)
 			status[rec] = ST_BAD_RECORD;
 		return;
 	}
-	const u8 *f = r + 12;
-	const u32 flen = rlen - 12;
-	if (uld32(f) != ZMT_ZSTD_MAGIC) {
+	const u8 *f = RUN ? stream : r + 12; /* (RUN: block positions are offsets into the stream, set block by block) */
+	u32 flen = rlen - 12;
+	if (!RUN && uld32(f) != ZMT_ZSTD_MAGIC) {
 		if (lane == 0)
 			status[rec] = ST_BAD_FRAME;
 		return;
 	}
-	const u32 fhd = uld8(f + 4);
+	const u32 fhd = RUN ? 0u : uld8(f + 4);
 	const u32 fcs = fhd >> 6, single = (fhd >> 5) & 1, did = fhd & 3, has_chk = (fhd >> 2) & 1;
 	u32 hp = 5;
 	u64 window = 0, content = ~0ull;
-	{
+	if (!RUN) {
 		const u32 did_len = did == 3 ? 4 : did, fcs_len = fcs == 0 ? single : (1u << fcs);
 		if ((fhd & 8) || flen < 5 + (1 - single) + did_len + fcs_len) {
 			if (lane == 0)
@@ -169,7 +213,7 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 			status[rec] = ST_SIZE_MISMATCH;
 		return;
 	}
-	const u32 block_max = window < Z_BLOCK_MAX ? (u32)window : Z_BLOCK_MAX;
+	u32 block_max = window < Z_BLOCK_MAX ? (u32)window : Z_BLOCK_MAX;
 
 	u32 rep0 = 1, rep1 = 4, rep2 = 8;
 	bool huf_ok = false;
@@ -182,15 +226,52 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 	bool my_tab_ok = false; /* lanes 0..2: state of the LL / OF / ML table this lane builds */
 	bool my_tab_pre = false; /* ... and whether it currently holds the predefined distribution */
 	int my_tab_log = 0;
-	u32 opos = 0, ip = hp;
+	u32 opos = run_hist, ip = hp;
 	/* sequences decoded ahead by zmt_zstd_seq_kernel (zstd_dec_seq.hip): hdr[i] != 0 says block i's are at seq[hdr[i] - 1] */
-	const bool pre_on = seqbuf != nullptr && zs_eligible(seqcap, out_off[rec], cap);
+	const bool pre_on = !RUN && seqbuf != nullptr && zs_eligible(seqcap, out_off[rec], cap);
 	const u32 *pre_hdr = pre_on ? (const u32 *)zs_region(seqbuf, out_off[rec]) : nullptr;
 	const u64 *pre_seq = pre_on ? zs_region(seqbuf, out_off[rec]) + zs_nhdr(cap) / 2 : nullptr;
 	const u32 pre_nhdr = pre_on ? zs_nhdr(cap) : 0;
 	u32 bi = 0; /* index of the block, counting every block of the frame */
+	if constexpr (RUN) {
+		/* ---- what the frame's earlier runs left: repeat offsets, the Huffman table, the three FSE tables ---- */
+		if (!(run_flags & ZR_FIRST)) {
+			if (cy->corrupt)
+				stc = ZBAD(); /* an earlier run of this frame failed */
+			rep0 = cy->rep[0];
+			rep1 = cy->rep[1];
+			rep2 = cy->rep[2];
+			huf_ok = cy->huf_ok != 0 && cy->huf_log <= (u32)LDS::hcap;
+			huf_log = huf_ok ? (int)cy->huf_log : 0;
+			if (lane < 3) {
+				my_tab_ok = cy->tab_ok[lane] != 0 &&
+					    cy->tab_log[lane] <= (u32)(lane == 0 ? LDS::llcap : lane == 1 ? LDS::ofcap : LDS::mlcap);
+				my_tab_log = my_tab_ok ? (int)cy->tab_log[lane] : 0;
+				my_tab_pre = cy->tab_pre[lane] != 0;
+			}
+			for (u32 i = (u32)lane; i < (1u << LDS::hcap); i += 64)
+				L.huf[i] = cy->huf[i];
+			for (u32 i = (u32)lane; i < (1u << LDS::llcap); i += 64) {
+				L.ll[i] = cy->ll[i];
+				L.ml[i] = cy->ml[i];
+			}
+			for (u32 i = (u32)lane; i < (1u << LDS::ofcap); i += 64)
+				L.of[i] = cy->of[i];
+			wv_sync();
+		}
+	}
 
-	for (;;) {
+	for (; !RUN || (bi < run_count && stc == ST_OK);) {
+		if constexpr (RUN) {
+			const ZBlock B = blocks[run_first + bi];
+			if (B.src_off > stream_bytes || B.src_len > stream_bytes - B.src_off || B.block_max > Z_BLOCK_MAX) {
+				stc = ST_BAD_RECORD;
+				break;
+			}
+			ip = (u32)B.src_off;
+			flen = ip + B.src_len;
+			block_max = B.block_max;
+		}
 		if (flen - ip < 3) {
 			stc = ZBAD();
 			break;
@@ -308,7 +389,7 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 				/* Raw literals (a unit whose literals did not compress): the blocks that follow the
 				 * same way still share the predefined sequence tables; list them for the unit-wide
 				 * sequence decode below (same records as the Huffman look-ahead writes) */
-				if (sq_left == 0 && !last) {
+				if (!RUN && sq_left == 0 && !last) {
 					u32 *pre = (u32 *)L.w;
 					wv_sync();
 					if (lane == 0) {
@@ -388,7 +469,7 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 				 * reuse it; four lanes per block decode up to 64 streams side by side instead of 4.
 				 * Anything odd in a block ahead just ends the look-ahead there: the block is then
 				 * decoded (and judged) when its turn comes. */
-				if (ltype == 2 && nstreams == 4 && !last && lcsz >= tree + 10u) {
+				if (!RUN && ltype == 2 && nstreams == 4 && !last && lcsz >= tree + 10u) {
 					u32 *pre = (u32 *)L.w; /* the weights are in the table now */
 					wv_sync();
 					if (lane == 0) {
@@ -863,7 +944,7 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 				 * idle) decode up to 16 blocks side by side into the record's scratch, 8 bytes a
 				 * sequence (ll | ml << 18 | offset value << 36); the blocks then only execute.
 				 * As with the literals, anything odd ends the unit before that block. */
-				if (unit_head) {
+				if (!RUN && unit_head) {
 					unit_head = false;
 					sq_left = 0;
 					if ((all_pre || all_fit) && unit_n) {
@@ -1263,8 +1344,46 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 			ip += bsize;
 		}
 		bi++;
-		if (last)
+		if constexpr (RUN) {
+			if (ip != flen) {
+				stc = ZBAD(); /* the table entry is not the block its header describes */
+				break;
+			}
+		} else if (last) {
 			break;
+		}
+	}
+	if constexpr (RUN) {
+		/* ---- the run's verdict, and the state for the frame's next run ---- */
+		wv_sync();
+		if (!(run_flags & ZR_LAST)) {
+			if (lane == 0) {
+				cy->rep[0] = rep0;
+				cy->rep[1] = rep1;
+				cy->rep[2] = rep2;
+				cy->huf_ok = huf_ok;
+				cy->huf_log = (u32)huf_log;
+				cy->corrupt = stc != ST_OK;
+			}
+			if (lane < 3) {
+				cy->tab_ok[lane] = my_tab_ok;
+				cy->tab_log[lane] = (u32)my_tab_log;
+				cy->tab_pre[lane] = my_tab_pre;
+			}
+			for (u32 i = (u32)lane; i < (1u << LDS::hcap); i += 64)
+				cy->huf[i] = L.huf[i];
+			for (u32 i = (u32)lane; i < (1u << LDS::llcap); i += 64) {
+				cy->ll[i] = L.ll[i];
+				cy->ml[i] = L.ml[i];
+			}
+			for (u32 i = (u32)lane; i < (1u << LDS::ofcap); i += 64)
+				cy->of[i] = L.of[i];
+		}
+		if (lane == 0) {
+			out_len[rec] = opos - run_hist;
+			status[rec] = stc;
+		}
+		return;
 	}
 	ZP(6);
 #ifndef ZMT_EMU
@@ -1349,6 +1468,19 @@ zmt_zstd_dec_kernel_prof(const u8 *__restrict__ stream, u64 stream_bytes, const 
 			    status, chk_expect, chk_valid, prof, seqbuf, seqcap);
 }
 #endif
+
+/* One wave per run of blocks, full-size tables: status[r] = GPUMT_ST_OK / BAD_BLOCK / BAD_RECORD (a table entry that
+ * leaves the stream or the output), run_len[r] = bytes decoded.  A match may read the run's `hist` bytes in front of its
+ * output and no further; a treeless or Repeat_Mode block whose table neither this run nor the carry holds is BAD_BLOCK. */
+extern "C" __global__ void __launch_bounds__(64)
+zmt_zstd_dec_run_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const ZBlock *__restrict__ blocks, u32 nblk,
+			const ZRun *__restrict__ runs, u32 nrun, u8 *out_base, u64 out_bytes, u8 *carry,
+			u32 *__restrict__ run_len, u32 *__restrict__ status, u8 *__restrict__ litbuf)
+{
+	__shared__ __attribute__((aligned(16))) ZLds L;
+	zstd_dec_body<false, ZLds, true>(L, 0u, stream, stream_bytes, nullptr, nullptr, nrun, out_base, nullptr, run_len, litbuf,
+					 status, nullptr, nullptr, nullptr, nullptr, 0, blocks, nblk, runs, out_bytes, carry);
+}
 
 /* ------------------------------------------------------------------ XXH64 content checksum
  * Four lanes per record = the four accumulators of XXH64 (one 32-byte stripe per step); only records
@@ -1460,3 +1592,194 @@ zmt_zstd_probe_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec
 	out_len[i] = n;
 	status[i] = st;
 }
+
+/*
+ * XXH64 (seed 0) with carried state (gpumt_xxh64_carry): the content checksum of a plain .zst frame that is decoded run
+ * after run, as zmt_xxh32_carry_kernel (xxh32.hip) is for .lz4.  One wave per job: lanes 0..3 run the four accumulators
+ * over the 32-byte stripes, the up to 31 bytes that do not fill a stripe wait in the state.  A state is 20 words in device
+ * memory: acc[4] (lo, hi), total length (lo, hi), pending count, spare, 32 pending bytes.  Jobs of one launch run side by
+ * side, so the one that reads a carried state and the one that leaves one name different slots.  Same job record and flags
+ * as the XXH32 call; `expect` is compared with the low 32 bits, which is what a zstd frame stores.
+ */
+struct Xxh64Job { /* == gpumt_xxh32_job */
+	u64 off;
+	u32 len, flags, expect, reserved;
+};
+#define X64J_RESET 1u
+#define X64J_FINAL 2u
+#define X64J_VERIFY 4u
+#define X64J_IN(f) (((f) >> 8) & 1u)
+#define X64J_OUT(f) (((f) >> 9) & 1u)
+#define X64_STATE_WORDS 20
+
+extern "C" __global__ void __launch_bounds__(64)
+zmt_xxh64_carry_kernel(const u8 *__restrict__ base, u64 base_bytes, const Xxh64Job *__restrict__ jobs, u32 njobs,
+		       u32 *__restrict__ states, u32 *__restrict__ digest, u32 *__restrict__ verdict)
+{
+	__shared__ __attribute__((aligned(8))) u8 tail[32];
+	const u32 j = blockIdx.x;
+	const int lane = wv_lane();
+	if (j >= njobs)
+		return;
+	const Xxh64Job J = jobs[j];
+	if (J.off > base_bytes || J.len > base_bytes - J.off) {
+		if (lane == 0) {
+			digest[j] = 0;
+			verdict[j] = ST_BAD_RECORD;
+		}
+		return;
+	}
+	const u32 a = (u32)lane & 3;
+	const u32 *sin = states + X64_STATE_WORDS * X64J_IN(J.flags);
+	u32 *sout = states + X64_STATE_WORDS * X64J_OUT(J.flags);
+	u64 acc = a == 0 ? X64_1 + X64_2 : a == 1 ? X64_2 : a == 2 ? 0ull : 0ull - X64_1;
+	u32 npend = 0;
+	u64 total = 0;
+	if (!(J.flags & X64J_RESET)) {
+		acc = (u64)sin[2 * a] | (u64)sin[2 * a + 1] << 32;
+		total = (u64)sin[8] | (u64)sin[9] << 32;
+		npend = sin[10] & 31u;
+		if (lane < 8)
+			*(u32 *)(tail + 4 * lane) = sin[12 + lane];
+	}
+	wv_sync();
+	const u8 *p = base + J.off;
+	u32 len = J.len;
+	total += len;
+	/* complete the pending stripe first: byte k of it is byte k - npend of the piece */
+	if (npend) {
+		const u32 take = 32 - npend < len ? 32 - npend : len;
+		if ((u32)lane >= npend && (u32)lane < npend + take)
+			tail[lane] = p[(u32)lane - npend];
+		wv_sync();
+		p += take;
+		len -= take;
+		npend += take;
+		if (npend == 32) {
+			acc = x64_round(acc, *(const u64 *)(tail + 8 * a));
+			npend = 0;
+		}
+		wv_sync();
+	}
+	if (lane < 4) {
+		const u8 *q = p + 8 * a;
+		u32 ns = len >> 5, s = 0;
+		for (; s + 8 <= ns; s += 8) {
+			u64 x[8];
+			for (u32 k = 0; k < 8; k++)
+				x[k] = ld64u(q + 32 * k);
+			for (u32 k = 0; k < 8; k++)
+				acc = x64_round(acc, x[k]);
+			q += 256;
+		}
+		for (; s < ns; s++) {
+			acc = x64_round(acc, ld64u(q));
+			q += 32;
+		}
+	}
+	if (npend == 0) { /* (else the piece ended inside the pending stripe: len is 0) */
+		npend = len & 31;
+		if ((u32)lane < npend)
+			tail[lane] = p[(len & ~31u) + (u32)lane];
+	}
+	wv_sync();
+	if (J.flags & X64J_FINAL) {
+		const u64 v1 = shfl64(acc, 0), v2 = shfl64(acc, 1), v3 = shfl64(acc, 2), v4 = shfl64(acc, 3);
+		if (lane == 0) {
+			u64 h;
+			if (total >= 32) {
+				h = rotl64(v1, 1) + rotl64(v2, 7) + rotl64(v3, 12) + rotl64(v4, 18);
+				h = x64_merge(h, v1);
+				h = x64_merge(h, v2);
+				h = x64_merge(h, v3);
+				h = x64_merge(h, v4);
+			} else {
+				h = X64_5;
+			}
+			h += total;
+			u32 t = 0;
+			for (; t + 8 <= npend; t += 8)
+				h = rotl64(h ^ x64_round(0, *(const u64 *)(tail + t)), 27) * X64_1 + X64_4;
+			if (t + 4 <= npend) {
+				h = rotl64(h ^ (u64)*(const u32 *)(tail + t) * X64_1, 23) * X64_2 + X64_3;
+				t += 4;
+			}
+			for (; t < npend; t++)
+				h = rotl64(h ^ (u64)tail[t] * X64_5, 11) * X64_1;
+			h ^= h >> 33;
+			h *= X64_2;
+			h ^= h >> 29;
+			h *= X64_3;
+			h ^= h >> 32;
+			digest[j] = (u32)h;
+			verdict[j] = (J.flags & X64J_VERIFY) && (u32)h != J.expect ? ST_BAD_CHECKSUM : ST_OK;
+		}
+	} else {
+		if (lane < 4) {
+			sout[2 * a] = (u32)acc;
+			sout[2 * a + 1] = (u32)(acc >> 32);
+		}
+		if (lane < 8)
+			sout[12 + lane] = (u32)lane * 4 < npend ? *(const u32 *)(tail + 4 * lane) : 0u;
+		if (lane == 0) {
+			sout[8] = (u32)total;
+			sout[9] = (u32)(total >> 32);
+			sout[10] = npend;
+			sout[11] = 0;
+			digest[j] = 0;
+			verdict[j] = ST_OK;
+		}
+	}
+}
+
+#ifdef ZMT_EMU
+/* TEST HARNESS ONLY (tests/emu compiles this file as host C++): the two block-level calls over the fiber emulator, with
+ * the shapes of include/gpumt.h, as the ones at the end of lz4_dec.hip and xxh32.hip.  Never part of the product. */
+#include <vector>
+#include "../../../include/gpumt.h"
+extern "C" {
+void emu_zstd_decompress_blocks(const u8 *stream, u64 stream_bytes, const void *blocks, u32 nblk, const void *runs, u32 nrun,
+				u8 *out, u64 out_bytes, u8 *carry, u32 *run_len, u32 *status)
+{
+	std::vector<u8> lit((size_t)nrun * Z_RUN_LITSLOT, 0xA5); /* scratch starts as garbage */
+	u8 *litp = lit.data();
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_zstd_dec_run_kernel(stream, stream_bytes, (const ZBlock *)blocks, nblk, (const ZRun *)runs, nrun, out, out_bytes,
+					carry, run_len, status, litp);
+	});
+}
+
+void emu_xxh64_carry(const u8 *base, u64 base_bytes, const void *jobs, u32 njobs, u32 *states, u32 *digest, u32 *verdict)
+{
+	emu::launch(emu::dim3{njobs, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_xxh64_carry_kernel(base, base_bytes, (const Xxh64Job *)jobs, njobs, states, digest, verdict); });
+}
+
+int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const gpumt_zstd_block *d_blocks,
+				 size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun, void *d_out, size_t out_bytes,
+				 void *d_carry, uint32_t *d_run_len, uint32_t *d_status, int s)
+{
+	static_assert(sizeof(gpumt_zstd_block) == sizeof(ZBlock) && sizeof(gpumt_zstd_run) == sizeof(ZRun) &&
+			      GPUMT_ZSTD_CARRY_BYTES == sizeof(ZCarry) && GPUMT_ZSTD_RUN_SCRATCH == Z_RUN_LITSLOT,
+		      "table layout");
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_stream || !d_blocks || !d_runs || !d_out || !d_carry || !d_run_len ||
+	    !d_status || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX || stream_bytes > 0xFFFFFFF0u)
+		return GPUMT_E_ARG;
+	emu_zstd_decompress_blocks((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
+				   out_bytes, (u8 *)d_carry, d_run_len, d_status);
+	return GPUMT_OK;
+}
+
+int gpumt_xxh64_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
+		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int s)
+{
+	static_assert(sizeof(gpumt_xxh32_job) == sizeof(Xxh64Job) && GPUMT_XXH64_STATE_WORDS == X64_STATE_WORDS, "table layout");
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_base || !d_jobs || !d_states || !d_digest || !d_verdict ||
+	    njobs > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if (njobs)
+		emu_xxh64_carry((const u8 *)d_base, base_bytes, d_jobs, (u32)njobs, d_states, d_digest, d_verdict);
+	return GPUMT_OK;
+}
+}
+#endif

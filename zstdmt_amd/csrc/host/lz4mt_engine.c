@@ -75,7 +75,6 @@ const char *LZ4MT_getErrorString(size_t code)
 #define MT_DECOMPRESS_BATCH gpumt_lz4_decompress_batch
 #define MT_FRAME_MAGIC LZ4FMT_MAGICNUMBER
 #define MT_PLAIN_REQUEST(ctx) ((size_t)(ctx)->inputsize) /* inputsize requests, lz4-mt_decompress.c:462-476 */
-#define MT_PLAIN_FIRST_FILLS 0
 #define MT_PLAIN_PIECE(ctx) ((ctx)->inputsize < 65536 ? (size_t)65536 : (size_t)(ctx)->inputsize)
 #define MT_PLAIN_ENTER(ctx, nfirst) ((ctx)->insize = (nfirst), (ctx)->outsize = 0)
 #define MT_PLAIN_COUNT_FAILED_WRITE 1
@@ -101,9 +100,7 @@ static size_t d12_status_error(uint32_t st)
 	return ERROR(compression_library);
 }
 
-/* plain .lz4 streams (typically 4 MiB blocks and no content size) are decoded block by block, mt_lz4_plain.inc;
- * mt_records12.inc's frame-per-record plain path is left out */
-#define MT_PLAIN_BLOCKS 1
+/* plain .lz4 streams (typically 4 MiB blocks and no content size) are decoded block by block, mt_lz4_plain.inc */
 static size_t plain_bad_frame(void) { return ERROR(compression_library); }
 
 #include "mt_records12.inc"

@@ -1,7 +1,8 @@
 /*
- * mt_frame_extent.h -- the frame splitters of the plain-stream paths (plain_decompress, mt_records12.inc):
- * where the LZ4 / zstd frame at p ends and how many bytes it can decode to, found by walking its block
- * headers on the host.  Pure functions over bytes: nothing of the device boundary is needed here
+ * mt_frame_extent.h -- frame splitters: where the LZ4 / zstd frame at p ends and how many bytes it can decode
+ * to, found by walking its block headers on the host (zstd-mt records whose frame states no content size,
+ * d12_out_size in zstdmt_engine.c; the plain-stream paths walk block by block themselves, mt_lz4_plain.inc and
+ * mt_zstd_plain.inc).  Pure functions over bytes: nothing of the device boundary is needed here
  * (tests/host/extent_harness.c runs them on the CPU).
  */
 #ifndef ZMT_MT_FRAME_EXTENT_H

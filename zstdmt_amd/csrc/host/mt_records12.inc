@@ -1,10 +1,10 @@
 /*
  * mt_records12.inc -- the decompress half of the codecs whose records carry a 12-byte header (lz4-mt, zstd-mt):
- * <PREFIX>_createDCtx / freeDCtx / Get*DCtx, the record pipeline (d12_run) and the plain-stream path
- * (plain_decompress).  The reference has this logic once per codec (lib/lz4-mt_decompress.c:165-567,
- * lib/zstd-mt_decompress.c:209-549,552-687); here it is one text, included after mt_compress.inc by lz4mt_engine.c
- * and zstdmt_engine.c, which keep <PREFIX>_decompressDCtx (the sniff) to themselves.  On top of mt_compress.inc's
- * parameters:
+ * <PREFIX>_createDCtx / freeDCtx / Get*DCtx, the record pipeline (d12_run) and the writer of the plain-stream paths
+ * (plain_write).  The reference has this logic once per codec (lib/lz4-mt_decompress.c:165-567,
+ * lib/zstd-mt_decompress.c:209-549); here it is one text, included after mt_compress.inc by lz4mt_engine.c
+ * and zstdmt_engine.c, which keep <PREFIX>_decompressDCtx (the sniff) to themselves and bring their plain path, block
+ * by block, behind this file (mt_lz4_plain.inc, mt_zstd_plain.inc).  On top of mt_compress.inc's parameters:
  *
  *   MT_ERRCODE                  the library's global for a codec-level error (lz4mt_errcode / zstdmt_errcode)
  *   MT_D_DEFAULT_INPUTSIZE      createDCtx's inputsize for 0
@@ -13,22 +13,17 @@
  *                               visits some of them)
  *   MT_DECOMPRESS_BATCH         gpumt_*_decompress_batch
  *   MT_FRAME_MAGIC              first four bytes of a frame the plain path takes
- *   MT_PLAIN_BLOCKS             (optional) the including file brings its own plain path (lz4-mt: mt_lz4_plain.inc, block by
- *                               block); plain_decompress and its two hooks are left out, plain_write stays
- *   MT_PLAIN_VARIANT            (optional) kernel family whose variant 1 the plain path forces around its batches
  *   MT_PLAIN_REQUEST(ctx)       bytes per fn_read of the plain path
- *   MT_PLAIN_FIRST_FILLS        1: the first request is shortened by the bytes that came with the sniff
  *   MT_PLAIN_PIECE(ctx)         largest fn_write of the plain path
  *   MT_PLAIN_ENTER(ctx, nfirst) the counters when the plain path starts
  *   MT_PLAIN_COUNT_FAILED_WRITE 1: outsize counts a piece whose fn_write failed
  *
- * and four hooks, defined by the including file before the include:
+ * and three hooks, defined by the including file before the include:
  *
  *   size_t d12_out_size(const uint8_t *frame, uint32_t csize, uint64_t *osz, int *unsized)
  *                               what a record decodes to; 0 or the error to return.  *unsized = 1: *osz is a capacity
  *                               and the decoder reports the size
  *   size_t d12_status_error(uint32_t st)        a record's device status (not GPUMT_ST_OK) -> library error
- *   size_t plain_frame_extent(const uint8_t *p, size_t n, uint64_t *bound)     mt_frame_extent.h's contract
  *   size_t plain_bad_frame(void)                the error for bytes that cannot be split into frames
  *
  * Plain C, no HIP header.
@@ -304,9 +299,8 @@ static size_t d12_run(MTP(DCtx) *ctx, MTP(RdWr_t) *rdwr)
  * thread with the codec's streaming decoder (st_decompress, lz4-mt_decompress.c:391-483, zstd-mt_decompress.c:552-687):
  * files of the lz4 / zstd tools and libraries, any number of frames, possibly without a content size and with
  * skippable frames in between.  Here the input is read about one batch ahead (same request sizes as the reference),
- * split into frames on the host by walking the block headers (mt_frame_extent.h) and decoded by the device kernels,
- * one wave per frame; a frame that does not state its content size gets the sum of its block bounds as capacity and
- * the decoder reports the size.  Output leaves in pieces like the reference's; GetFrames stays 0 as in the reference
+ * walked block by block on the host and decoded by the device's block-level calls (mt_lz4_plain.inc,
+ * mt_zstd_plain.inc).  Output leaves in pieces like the reference's; GetFrames stays 0 as in the reference
  * (st_decompress counts no frames). */
 static size_t plain_write(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *p, size_t n)
 {
@@ -329,182 +323,3 @@ static size_t plain_write(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *p, siz
 	}
 	return 0;
 }
-
-#ifndef MT_PLAIN_BLOCKS
-/* first[0..nfirst) came with the sniff; at_eof: the sniff already hit the end of the input */
-static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *first, size_t nfirst, int at_eof)
-{
-	const size_t req = MT_PLAIN_REQUEST(ctx);
-	size_t cap = MT_PLAIN_FIRST_FILLS ? req : req + nfirst, n = nfirst, err = 0, ip = 0;
-	uint8_t *raw = (uint8_t *)malloc(cap);
-	size_t want_ahead = BATCH_BYTES; /* input buffered before a round of frames is split off */
-	int eof = at_eof, first_read = MT_PLAIN_FIRST_FILLS;
-	struct dslot *s = &ctx->s[0];
-	gpumt_ctx *g = mt_gpu_of(&ctx->gpus, 0);
-	if (!raw)
-		return MTP(ERROR)(memory_allocation);
-	memcpy(raw, first, nfirst);
-	MT_PLAIN_ENTER(ctx, nfirst);
-	/* The input is consumed incrementally: read (in the reference's request sizes, lz4-mt_decompress.c:462-476; zstd: the
-	 * first request fills the first buffer behind the sniffed bytes, zstd-mt_decompress.c:590-609) until about one
-	 * batch of input is buffered or the stream ends, decode the complete frames of what is there, keep
-	 * the incomplete tail, repeat -- the host holds about two batches of input plus the largest
-	 * frame, not the whole stream, and output starts before the input ends. */
-	for (;;) {
-	int need_more = 0;
-	while (!eof && n - ip < want_ahead) {
-		MTP(Buffer) b;
-		int rv;
-		const size_t want = first_read ? req - nfirst : req;
-		if (ip && ip == n) {
-			n = 0;
-			ip = 0;
-		}
-		if (n + want > cap) {
-			if (ip >= want) { /* drop what is decoded instead of growing */
-				memmove(raw, raw + ip, n - ip);
-				n -= ip;
-				ip = 0;
-			} else {
-				uint8_t *nr;
-				cap = cap * 2 + want;
-				nr = (uint8_t *)realloc(raw, cap);
-				if (!nr) {
-					free(raw);
-					return MTP(ERROR)(memory_allocation);
-				}
-				raw = nr;
-			}
-		}
-		b.buf = raw + n;
-		b.size = want;
-		b.allocated = want;
-		rv = io->fn_read(io->arg_read, &b);
-		if (rv != 0) {
-			free(raw);
-			return mt_error(rv);
-		}
-		first_read = 0;
-		if (b.size == 0) {
-			eof = 1;
-			break;
-		}
-		n += b.size;
-		ctx->insize += b.size;
-	}
-	/* ---- frames, in batches the device buffers can hold ---- */
-	while (ip < n && !err) {
-		size_t in_bytes = 0, out_bytes = 0, nrec = 0, jp = ip;
-		if (dbuf_want(g, &s->meta, D_META_BYTES(BATCH_MAXREC), 1, 1)) {
-			err = MTP(ERROR)(memory_allocation);
-			break;
-		}
-		/* pass 1: extents of the frames of this batch */
-		while (jp < n && nrec < BATCH_MAXREC) {
-			uint64_t bound = 0;
-			size_t flen;
-			if (n - jp >= 8 && (rd32(raw + jp) & 0xFFFFFFF0u) == MT_MAGIC_SKIPPABLE) {
-				const size_t sk = 8 + (size_t)rd32(raw + jp + 4);
-				if (sk > n - jp) {
-					if (!eof)
-						need_more = 1; /* the rest of it has not been read yet */
-					else
-						err = MTP(ERROR)(compression_library);
-					break;
-				}
-				jp += sk;
-				continue;
-			}
-			if (!eof && n - jp <= 0xFFFFFFF0u &&
-			    (n - jp < 8 || (rd32(raw + jp) == MT_FRAME_MAGIC && !plain_frame_extent(raw + jp, n - jp, &bound)))) {
-				need_more = 1; /* an incomplete frame: wait for the rest (a damaged one is EXTENT_INVALID, below) */
-				break;
-			}
-			if (n - jp < 4 || rd32(raw + jp) != MT_FRAME_MAGIC ||
-			    !(flen = plain_frame_extent(raw + jp, n - jp, &bound)) || flen == EXTENT_INVALID ||
-			    flen > 0xFFFFFFF0u || bound > 0x7FFFFFFFull) {
-				err = plain_bad_frame();
-				break;
-			}
-			if (nrec && (in_bytes + 12 + flen > BATCH_BYTES || out_bytes + bound > 4 * BATCH_BYTES))
-				break;
-			m_rec_off(&s->meta, 0)[nrec] = in_bytes;
-			m_rec_len(&s->meta, 0)[nrec] = (uint32_t)(12 + flen);
-			m_out_off(&s->meta, 0)[nrec] = out_bytes;
-			m_out_len(&s->meta, 0)[nrec] = (uint32_t)bound;
-			in_bytes += 12 + flen;
-			out_bytes += (size_t)bound;
-			nrec++;
-			jp += flen;
-		}
-		if (err)
-			break;
-		if (!nrec) { /* only skippable frames were left */
-			ip = jp;
-			if (need_more)
-				break;
-			continue;
-		}
-		m_out_off(&s->meta, 0)[nrec] = out_bytes;
-		if (dbuf_want(g, &s->in, in_bytes + 512, 1, 1) || dbuf_want(g, &s->out, out_bytes + 64, 1, 1) ||
-		    dbuf_want(g, &s->status, nrec * 4 + 64, 1, 1)) {
-			err = MTP(ERROR)(memory_allocation);
-			break;
-		}
-		/* pass 2: records = 12-byte skippable header + frame, the layout the kernels take */
-		{
-			size_t k = 0, q = ip;
-			while (k < nrec) {
-				if ((rd32(raw + q) & 0xFFFFFFF0u) == MT_MAGIC_SKIPPABLE) {
-					q += 8 + (size_t)rd32(raw + q + 4);
-					continue;
-				}
-				const uint32_t flen = m_rec_len(&s->meta, 0)[k] - 12;
-				uint8_t *rec = (uint8_t *)s->in.h + m_rec_off(&s->meta, 0)[k];
-				mt_rec12_header(rec, flen);
-				memcpy(rec + 12, raw + q, flen);
-				q += flen;
-				k++;
-			}
-		}
-		s->nrec = nrec;
-		s->in_bytes = in_bytes;
-		s->out_bytes = out_bytes;
-		{
-			/* everything on stream 0; out_len always comes back (sizes of unsized frames) */
-#ifdef MT_PLAIN_VARIANT
-			/* frame-serial kernel for every record: block sizes and counts are arbitrary here */
-			const int prev = gpumt_set_variant(g, MT_PLAIN_VARIANT, 1);
-#endif
-			int rc = d_batch(g, s, 0, 0, 0, 1);
-			rc |= gpumt_stream_sync(g, 0);
-#ifdef MT_PLAIN_VARIANT
-			gpumt_set_variant(g, MT_PLAIN_VARIANT, prev);
-#endif
-			if (rc) {
-				err = MTP(ERROR)(compression_library);
-				break;
-			}
-		}
-		for (size_t i = 0; i < nrec && !err; i++) {
-			const uint32_t st = ((const uint32_t *)s->status.h)[i];
-			if (st != GPUMT_ST_OK) {
-				MT_ERRCODE = st;
-				err = MTP(ERROR)(compression_library);
-				break;
-			}
-			err = plain_write(ctx, io, (const uint8_t *)s->out.h + m_out_off(&s->meta, 0)[i], m_out_len(&s->meta, 0)[i]);
-		}
-		ip = jp;
-		if (need_more)
-			break;
-	}
-	if (err || (eof && ip >= n))
-		break;
-	if (need_more && n - ip >= want_ahead)
-		want_ahead = (n - ip) * 2; /* a frame larger than what is buffered: read on */
-	}
-	free(raw);
-	return err;
-}
-#endif /* MT_PLAIN_BLOCKS */

@@ -10,9 +10,9 @@
  *              record (:221-353); one fn_write per frame in order.
  * Stream layouts accepted by decompress: the one the compressor writes ("pzstd style": skippable
  * frame first, :251-284) and the old "zstdmt style" (a 9-byte empty zstd frame in front, :225-249).
- * Plain .zst streams (the reference's single-threaded path) are split into frames on the
- * host and decoded by the same kernels (plain_decompress, mt_records12.inc).
- * The compress half is mt_compress.inc, the record pipeline and the plain-stream path are mt_records12.inc (both shared
+ * Plain .zst streams (the reference's single-threaded path) are walked block by block on the
+ * host and decoded run by run, frames of any size (plain_decompress, mt_zstd_plain.inc).
+ * The compress half is mt_compress.inc, the record pipeline is mt_records12.inc (both shared
  * with lz4mt_engine.c); this file holds what is zstd-mt's own: the error strings, the parameters and hooks of the two
  * texts, the content size of a frame and the 16-byte sniff of ZSTDCB_decompressDCtx.
  * Plain C, no HIP header.
@@ -108,7 +108,6 @@ static const int window_log[] = {19, 19, 20, 20, 20, 21, 21, 21, 21, 21, 22, 22,
 #define MT_DECOMPRESS_BATCH gpumt_zstd_decompress_batch
 #define MT_FRAME_MAGIC ZSTDCB_MAGICNUMBER_MAX
 #define MT_PLAIN_REQUEST(ctx) ((void)(ctx), (size_t)ZSTD_IN_CHUNK)
-#define MT_PLAIN_FIRST_FILLS 1 /* zstd-mt_decompress.c:590-609 */
 #define MT_PLAIN_PIECE(ctx) ((void)(ctx), (size_t)ZSTD_OUT_CHUNK)
 #define MT_PLAIN_ENTER(ctx, nfirst) ((ctx)->insize += (nfirst))
 #define MT_PLAIN_COUNT_FAILED_WRITE 0
@@ -146,12 +145,6 @@ static size_t d12_status_error(uint32_t st)
 	return ZSTDCB_ERROR(compression_library);
 }
 
-static size_t plain_frame_extent(const uint8_t *p, size_t n, uint64_t *bound)
-{
-	int sized;
-	return zstd_frame_extent(p, n, bound, &sized);
-}
-
 static size_t plain_bad_frame(void)
 {
 	zstdmt_errcode = GPUMT_ST_BAD_FRAME;
@@ -159,6 +152,7 @@ static size_t plain_bad_frame(void)
 }
 
 #include "mt_records12.inc"
+#include "mt_zstd_plain.inc"
 
 size_t ZSTDCB_decompressDCtx(ZSTDCB_DCtx *ctx, ZSTDCB_RdWr_t *rdwr)
 {

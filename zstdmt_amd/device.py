@@ -18,6 +18,13 @@ LZ4_BLOCK = np.dtype([("src_off", "<u8"), ("src_len", "<u4"), ("flags", "<u4"), 
 LZ4_RUN = np.dtype([("low", "<u8"), ("out_off", "<u8"), ("out_cap", "<u4"), ("first", "<u4"), ("count", "<u4"),
                     ("reserved", "<u4")])
 XXH32_JOB = np.dtype([("off", "<u8"), ("len", "<u4"), ("flags", "<u4"), ("expect", "<u4"), ("reserved", "<u4")])
+# gpumt_zstd_block / gpumt_zstd_run
+ZSTD_BLOCK = np.dtype([("src_off", "<u8"), ("src_len", "<u4"), ("block_max", "<u4")])
+ZSTD_RUN = np.dtype([("out_off", "<u8"), ("out_cap", "<u4"), ("hist", "<u4"), ("first", "<u4"), ("count", "<u4"),
+                     ("flags", "<u4"), ("carry", "<u4")])
+ZRUN_FIRST, ZRUN_LAST = 1, 2
+ZSTD_CARRY_BYTES = 9280
+XXH64_STATE_WORDS = 20
 LZ4B_STORED, LZ4B_CHECKSUM = 1, 2
 XXH_RESET, XXH_FINAL, XXH_VERIFY = 1, 2, 4
 
@@ -239,6 +246,60 @@ class Engine:
                 self.sync(0)
                 self._ck(self.L.gpumt_xxh32_carry(self.h, d_data.ptr, len(data), d_job.ptr, 1, d_states.ptr, d_dig.ptr,
                                                   d_ver.ptr, 0), "xxh32_carry")
+                at += n
+            return int(self.download(d_dig, 4, np.uint32)[0])
+        finally:
+            for b in (d_data, d_states, d_dig, d_ver, d_job):
+                b.free()
+
+    def zstd_decompress_blocks(self, stream: bytes, blocks, runs, out_bytes, history=b"", carry=None):
+        """gpumt_zstd_decompress_blocks over host bytes: `blocks` / `runs` are ZSTD_BLOCK / ZSTD_RUN arrays, `history` is
+        placed at the start of the output (what a continued run reads in front of its out_off), `carry` the 2 x
+        ZSTD_CARRY_BYTES an earlier call left (None: garbage).  -> (output area bytes, run_len[nrun], status[nrun],
+        carry bytes)"""
+        blocks = np.ascontiguousarray(blocks, ZSTD_BLOCK)
+        runs = np.ascontiguousarray(runs, ZSTD_RUN)
+        nblk, nrun = len(blocks), len(runs)
+        area = np.full(int(out_bytes) + 64, 0xCC, np.uint8)
+        area[:len(history)] = np.frombuffer(history, np.uint8)
+        cy = np.full(2 * ZSTD_CARRY_BYTES, 0xA5, np.uint8) if carry is None else np.frombuffer(carry, np.uint8)
+        d_stream = self.upload(stream) if stream else self.alloc(320)
+        d_blk, d_run, d_out = self.upload(blocks.view(np.uint8)), self.upload(runs.view(np.uint8)), self.upload(area, slack=0)
+        d_cy, d_rl, d_st = self.upload(cy), self.alloc(nrun * 4), self.alloc(nrun * 4)
+        try:
+            self._ck(self.L.gpumt_zstd_decompress_blocks(self.h, d_stream.ptr, len(stream), d_blk.ptr, nblk, d_run.ptr, nrun,
+                                                         d_out.ptr, int(out_bytes), d_cy.ptr, d_rl.ptr, d_st.ptr, 0),
+                     "zstd_decompress_blocks")
+            status = self.download(d_st, nrun * 4, np.uint32)
+            run_len = self.download(d_rl, nrun * 4, np.uint32)
+            raw = self.download(d_out, int(out_bytes) + 64)
+            cy_out = self.download(d_cy, 2 * ZSTD_CARRY_BYTES).tobytes()
+        finally:
+            for b in (d_stream, d_blk, d_run, d_out, d_cy, d_rl, d_st):
+                b.free()
+        assert (raw[int(out_bytes):] == 0xCC).all(), "decoder wrote past the end of its output"
+        return raw[:int(out_bytes)].tobytes(), run_len, status, cy_out
+
+    def xxh64_carry(self, data: bytes, pieces):
+        """low 32 bits of XXH64 of `data` continued over `pieces` (lengths that add up to len(data)), one gpumt_xxh64_carry
+        call per piece with the state carried on the device -> digest"""
+        assert sum(pieces) == len(data) and pieces
+        d_data = self.upload(data) if data else self.alloc(64)
+        d_states, d_dig, d_ver = self.alloc(2 * XXH64_STATE_WORDS * 4), self.alloc(4), self.alloc(4)
+        d_job = self.alloc(XXH32_JOB.itemsize)
+        try:
+            at, xs = 0, 0
+            for i, n in enumerate(pieces):
+                last = i == len(pieces) - 1
+                job = np.zeros(1, XXH32_JOB)
+                job["off"], job["len"] = at, n
+                job["flags"] = (XXH_RESET if i == 0 else xs << 8) | (XXH_FINAL if last else (xs ^ 1) << 9)
+                if not last:
+                    xs ^= 1
+                self._ck(self.L.gpumt_memcpy_h2d(self.h, d_job.ptr, job.ctypes.data, job.nbytes, 0), "h2d")
+                self.sync(0)
+                self._ck(self.L.gpumt_xxh64_carry(self.h, d_data.ptr, len(data), d_job.ptr, 1, d_states.ptr, d_dig.ptr,
+                                                  d_ver.ptr, 0), "xxh64_carry")
                 at += n
             return int(self.download(d_dig, 4, np.uint32)[0])
         finally:
