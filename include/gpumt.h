@@ -348,6 +348,33 @@ int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stre
 				 int stream);
 
 /*
+ * The same call with a block-parallel entropy stage in front of the runs: same arguments, contract, statuses, d_run_len and
+ * carry as gpumt_zstd_decompress_blocks -- a call of either kind may follow a call of the other on the same carry.  Three
+ * more launches on the same stream, none of which waits on another wave: one lane per block reads the block, literals and
+ * sequences headers; one wave per run finds, for every block, the earlier block of the same run in this call that
+ * describes the Huffman / LL / OF / ML table it uses (treeless literals, Repeat_Mode); one wave per Compressed_Block, all
+ * blocks of all runs side by side, decodes the block's Huffman literals and its FSE sequence bitstream into scratch.  The
+ * runs then decode one wave each as before, but a block the stage marked only builds its tables, copies its literals and
+ * executes its sequences (repeat offsets, matches): what is still one chain per frame.
+ * d_block_mark (nblk words, may be NULL) receives per block: bit 0 = its sequences were decoded ahead, bit 1 = its literals
+ * were (or are raw / RLE literals, which need no decoding).  A block is marked only when its tables, bitstreams and
+ * end-of-stream conditions were all clean; a Raw or RLE block, a block whose table was defined before this call (it is in
+ * the carry), a block with more than block_max / 4 sequences, and anything malformed are 0 and decoded -- and judged --
+ * exactly as gpumt_zstd_decompress_blocks does.
+ * Internal scratch: GPUMT_ZSTD_RUN_SCRATCH per run + GPUMT_ZSTD_PRE_SCRATCH(131072) + 52 bytes per block of the table, whatever
+ * the block's own size (the slots lie at one stride: 3 GiB for a table of 8192 blocks); when the device cannot provide it
+ * the call decodes serially (marks 0) rather than fail, keeps the scratch it has, and does not ask for that size again.
+ * GPUMT_ZSTD_RUN_PRE=0 in the environment or gpumt_set_variant(h, "zstd_run_pre", 0) turn the stage off: the call is then
+ * gpumt_zstd_decompress_blocks with every mark 0 (1 turns it on again; other values are refused).
+ */
+/* what a block of the table needs: its literals (128 KiB + slack) and block_max / 4 sequences of 8 bytes */
+#define GPUMT_ZSTD_PRE_SCRATCH(block_max) (131072u + 256u + 8u * ((block_max) / 4u))
+int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				     const gpumt_zstd_block *d_blocks, size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun,
+				     void *d_out, size_t out_bytes, void *d_carry, uint32_t *d_run_len, uint32_t *d_status,
+				     uint32_t *d_block_mark, int stream);
+
+/*
  * XXH64 (seed 0) with carried state, the content checksum of a zstd frame decoded over several calls: gpumt_xxh32_carry's
  * contract with the same job record and flags, a state of GPUMT_XXH64_STATE_WORDS words per slot (four 64-bit
  * accumulators, the total length, up to 31 pending bytes), and `expect` / d_digest are the low 32 bits of the hash --
@@ -424,7 +451,8 @@ int gpumt_xxh32_batch(gpumt_ctx *h, const void *d_base, const uint64_t *d_off,
  * (gpumt_set_variant("lz4_dec", 2)). */
 int gpumt_debug_counters(gpumt_ctx *h, unsigned long long *dst, int n);
 
-/* Kernel-variant selector for A/B measurements (0 = default). Returns previous value. */
+/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre": 1 = default, 0 = off, anything else is refused
+ * with -1 and changes nothing). Returns previous value. */
 int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant);
 
 #ifdef __cplusplus

@@ -5,6 +5,7 @@ another on the same streams: the tables of profiles/plain_zst_blocks.txt.
   python tools/plain_zst_bench.py --mib 256 --runs 3 --old path/to/parent/libzstdmt_amd.so [--new path] [--out file]
   python tools/plain_zst_bench.py --rss-mib 1024 --old ...      peak host RSS of one decode, either library
   python tools/plain_zst_bench.py --rle-blocks 16400            the hand-built frame of RLE blocks above 2 GiB (new only)
+  python tools/plain_zst_bench.py --small-mib 256 --old ...     the same text as frames of 192 KiB, one behind the other
 
 Every run is a process of its own (a library reads its batch size once; a fault ends one run, not the job) under a time
 limit; the two libraries alternate.  The callbacks copy up to 128 KiB per call, the library's piece size.  GPUMT_TRACE=1
@@ -84,7 +85,7 @@ def child(a, libpath, path, n, keep, trace):
     line = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else "(no output)"
     if p.returncode != 0 or not line.startswith("seconds"):
         return None, "exit %d %s %s" % (p.returncode, line, p.stderr[-300:]), []
-    return float(line.split()[1]), line, [t.strip() for t in p.stderr.splitlines() if "[zstdmt plain]" in t]
+    return float(line.split()[1]), line, [t.strip() for t in p.stderr.splitlines() if "[zstdmt plain" in t]
 
 
 def main():
@@ -92,6 +93,7 @@ def main():
     ap.add_argument("--mib", type=int, default=0)
     ap.add_argument("--rss-mib", type=int, default=0)
     ap.add_argument("--rle-blocks", type=int, default=0)
+    ap.add_argument("--small-mib", type=int, default=0)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--old", default=None)
     ap.add_argument("--new", default=os.path.join(ROOT, "zstdmt_amd", "lib", "libzstdmt_amd.so"))
@@ -110,14 +112,19 @@ def main():
         print(*x, file=out, flush=True)
     libs = ([("old", a.old)] if a.old else []) + [("new", a.new)]
     say("# old = %s\n# new = %s" % (a.old, a.new))
-    if a.mib:
-        n = a.mib << 20
+    if a.mib or a.small_mib:
+        n = (a.mib or a.small_mib) << 20
         data = cases.text(n)
-        say("# ZSTDCB_decompressDCtx, plain .zst, one frame of %d MiB of the bench text, memcpy callbacks" % a.mib)
+        small = 192 << 10  # many frames side by side: 1.5 blocks each, every frame a run of its own
+        say("# ZSTDCB_decompressDCtx, plain .zst, %s of %d MiB of the bench text, memcpy callbacks"
+            % ("one frame" if a.mib else "frames of %d KiB" % (small >> 10), n >> 20))
         say("# %d runs each, alternating old / new; GB/s of content" % a.runs)
-        for name, kw in STREAMS:
+        for name, kw in (STREAMS if a.mib else [("small_frames_level3", dict(level=3, checksum=0))]):
             path = os.path.join(a.tmp, "plain_%s.zst" % name)
-            fr = H.libzstd_frame(data, **kw)
+            if a.mib:
+                fr = H.libzstd_frame(data, **kw)
+            else:
+                fr = b"".join(H.libzstd_frame(data[i:i + small], **kw) for i in range(0, n, small))
             with open(path, "wb") as f:
                 f.write(fr)
             say("\n## %s: %d -> %d bytes" % (name, len(fr), n))

@@ -86,6 +86,12 @@ __global__ void zmt_zstd_seq_kernel(const u8 *, u64, const u64 *, const u32 *, u
 				    const u32 *, u8 *, u64);
 __global__ void zmt_zstd_dec_run_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
 					u64, u8 *, u32 *, u32 *, u8 *);
+__global__ void zmt_zstd_pre_classify_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, void *, u32 *, u32 *);
+__global__ void zmt_zstd_pre_resolve_kernel(const gpumt_zstd_run *, u32, u32, const void *, u32 *);
+__global__ void zmt_zstd_pre_entropy_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const void *, const u32 *, u8 *,
+					    u32 *);
+__global__ void zmt_zstd_dec_run_pre_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
+					    u64, u8 *, u32 *, u32 *, u8 *, const u32 *, const u32 *, const u8 *);
 __global__ void zmt_xxh64_carry_kernel(const u8 *, u64, const gpumt_xxh32_job *, u32, u32 *, u32 *, u32 *);
 __global__ void zmt_xxh64_verify_kernel(const u8 *, const u64 *, const u32 *, u32, const u32 *, const u32 *,
 					u32 *);
@@ -126,6 +132,8 @@ struct gpumt_ctx {
 	int hc_waves;     /* developer: grid of the LZ4HC encoder (0 = GPUMT_LZ4HC_WAVES) */
 	int zdec_variant; /* 0 = small-table kernel, then general; 1 = general only */
 	int zseq_variant; /* 0 = sequence pre-pass (zstd_dec_seq.hip) in front of the frame decoder; 1 = none */
+	int zrun_pre;     /* 1 = entropy pre-pass in front of the block runs (gpumt_zstd_decompress_blocks_pre); 0 = none */
+	size_t zrun_pre_refused; /* the smallest pre-pass scratch the device has refused (0 = none yet): not asked for again */
 	int sdec_variant; /* snappy decoder: 0 = element by element, 1 = 64 elements per batch (snappy.hip) */
 	int bdec_variant; /* brotli decoder: 0 = by batch size, 1 = the general kernel only, 2 = dec4 (four records per wave) + general for what it hands over */
 	int bdec_waves;   /* resident waves of the persistent brotli decoder kernel (whole device) */
@@ -278,6 +286,15 @@ int gpumt_open(int device, gpumt_ctx **out)
 		/* GPUMT_ZSTD_SEQ=1: no sequence pre-pass in front of the zstd frame decoder */
 		e = getenv("GPUMT_ZSTD_SEQ");
 		h->zseq_variant = e && *e ? atoi(e) : 0;
+		/* GPUMT_ZSTD_RUN_PRE=0: gpumt_zstd_decompress_blocks_pre decodes serially, without its entropy pre-pass */
+		e = getenv("GPUMT_ZSTD_RUN_PRE");
+		h->zrun_pre = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				h->zrun_pre = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PRE=%s ignored (0 or 1)\n", e);
+		}
 		/* GPUMT_BROTLI_DEC: 0 = the batch size chooses (default), 1 = the general kernel, 2 = dec4 first */
 		e = getenv("GPUMT_BROTLI_DEC");
 		h->bdec_variant = e && *e ? atoi(e) : 0;
@@ -1251,6 +1268,71 @@ int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stre
 	return GPUMT_OK;
 }
 
+/* scratch of the pre-pass, behind the runs' literal slots: slot | ZPre | def | mark per block (zstd_dec.hip) */
+#define ZPRE_STRIDE ((size_t)GPUMT_ZSTD_PRE_SCRATCH(131072u))
+#define ZPRE_REC 32u
+int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				     const gpumt_zstd_block *d_blocks, size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun,
+				     void *d_out, size_t out_bytes, void *d_carry, uint32_t *d_run_len, uint32_t *d_status,
+				     uint32_t *d_block_mark, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_stream || !d_blocks || !d_runs || !d_out || !d_carry || !d_run_len || !d_status ||
+	    nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX || stream_bytes > 0xFFFFFFF0u)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	/* the execute stage reads the slots of all its blocks, so the runs go in one launch: a table whose runs or blocks
+	 * would need more scratch than the device gives decodes serially */
+	const size_t lit_bytes = (nrun * (size_t)GPUMT_ZSTD_RUN_SCRATCH + 255) & ~(size_t)255;
+	const size_t pre_bytes = nblk * (ZPRE_STRIDE + ZPRE_REC + 16 + 4);
+	const size_t need = (lit_bytes + pre_bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
+	int ahead = h->zrun_pre != 0 && nblk != 0 && nrun <= 4096 && !(h->zrun_pre_refused && need >= h->zrun_pre_refused);
+	if (ahead && need > h->scratch_bytes[1][s]) {
+		/* the larger area first, the current one dropped only once it is there: a refusal leaves the serial call its
+		 * scratch, and a size the device has refused once is not asked for batch after batch */
+		void *p = dev_alloc(h, need);
+		if (!p) {
+			(void)hipGetLastError(); /* (a refused allocation is no error of this call) */
+			h->zrun_pre_refused = need;
+			ahead = 0;
+		} else {
+			if (h->scratch[1][s]) {
+				if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+					dev_free(h, p);
+					return GPUMT_E_HIP;
+				}
+				dev_free(h, h->scratch[1][s]);
+			}
+			h->scratch[1][s] = p;
+			h->scratch_bytes[1][s] = need;
+		}
+	}
+	if (!ahead) {
+		if (d_block_mark && nblk)
+			CK(hipMemsetAsync(d_block_mark, 0, nblk * 4, h->st[s]));
+		return gpumt_zstd_decompress_blocks(h, d_stream, stream_bytes, d_blocks, nblk, d_runs, nrun, d_out, out_bytes,
+						    d_carry, d_run_len, d_status, s);
+	}
+	u8 *lit = (u8 *)h->scratch[1][s], *slots = lit + lit_bytes;
+	void *pre = slots + nblk * ZPRE_STRIDE;
+	u32 *def = (u32 *)((u8 *)pre + nblk * ZPRE_REC), *mark = def + 4 * nblk;
+	PROF0(11);
+	hipLaunchKernelGGL(zmt_zstd_pre_classify_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, h->st[s],
+			   (const u8 *)d_stream, (u64)stream_bytes, d_blocks, (u32)nblk, pre, def, mark);
+	hipLaunchKernelGGL(zmt_zstd_pre_resolve_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], d_runs, (u32)nrun, (u32)nblk,
+			   (const void *)pre, def);
+	hipLaunchKernelGGL(zmt_zstd_pre_entropy_kernel, dim3((unsigned)nblk), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, (const void *)pre, (const u32 *)def, slots, mark);
+	hipLaunchKernelGGL(zmt_zstd_dec_run_pre_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out, (u64)out_bytes, (u8 *)d_carry,
+			   d_run_len, d_status, lit, (const u32 *)mark, (const u32 *)def, (const u8 *)slots);
+	if (d_block_mark)
+		CK(hipMemcpyAsync(d_block_mark, mark, nblk * 4, hipMemcpyDeviceToDevice, h->st[s]));
+	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
 int gpumt_xxh64_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
 		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int s)
 {
@@ -1500,6 +1582,11 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 	} else if (!strcmp(what, "zstd_seq")) {
 		prev = h->zseq_variant;
 		h->zseq_variant = variant;
+	} else if (!strcmp(what, "zstd_run_pre")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->zrun_pre;
+		h->zrun_pre = variant;
 	} else if (!strcmp(what, "snappy_dec")) {
 		prev = h->sdec_variant;
 		h->sdec_variant = variant;

@@ -77,6 +77,25 @@ struct ZCarry { /* GPUMT_ZSTD_CARRY_BYTES */
 };
 static_assert(sizeof(ZCarry) == 9280, "GPUMT_ZSTD_CARRY_BYTES in include/gpumt.h");
 #define Z_RUN_LITSLOT (Z_BLOCK_MAX + 256u) /* literal scratch per run = GPUMT_ZSTD_RUN_SCRATCH */
+/* The entropy pre-pass of a call's block table (gpumt_zstd_decompress_blocks_pre, the kernels at the end of this file): what
+ * the classify kernel found in a block's headers, one record per block of the table ... */
+struct ZPre {
+	u32 ok;    /* a Compressed_Block whose three headers parse; 0: left to the serial path */
+	u32 lit;   /* Literals_Block_Type | streams << 2 | bytes of the literals section header << 8 */
+	u32 regen, lcsz; /* Regenerated_Size, Compressed_Size (= regen for raw, 1 for RLE literals) */
+	u32 sq0;   /* the sequences section, from the start of the block's body */
+	u32 nseq;
+	u32 sqh;   /* bytes of Number_of_Sequences and the modes byte | Symbol_Compression_Modes << 8 */
+	u32 bsize;
+};
+/* ... the block that defines each table it uses (resolve kernel: def[4 b + k], k = Huffman, LL, OF, ML; the block's own index
+ * when it describes the table itself, ZPRE_NONE when no block of the same run in this call does), and its two slots: */
+#define ZPRE_NONE 0xFFFFFFFFu
+#define Z_PRE_SEQCAP(block_max) ((block_max) / 4u) /* sequences a block's slot holds; a denser block stays serial */
+#define Z_PRE_LIT (Z_BLOCK_MAX + 256u)
+#define Z_PRE_STRIDE (Z_PRE_LIT + 8u * Z_PRE_SEQCAP(Z_BLOCK_MAX)) /* literals | sequences = GPUMT_ZSTD_PRE_SCRATCH(128 KiB) */
+#define ZPRE_SEQ 1u /* mark bits: the block's sequences are in its slot ... */
+#define ZPRE_LIT 2u /* ... its literals are (or need no decoding: raw, RLE) */
 
 
 /* ------------------------------------------------------------------ the kernel */
@@ -108,14 +127,19 @@ static inline u32 zbad_(int line)
 /* RUN: the same decoder started at a block header instead of a frame header (zmt_zstd_dec_run_kernel, at the end of this
  * file): "record" rec is run rec of `runs`, its blocks are entries of `blocks`, out_len receives the run's length, and what
  * a frame's later blocks may refer to travels in a ZCarry.  No units and no pre-pass there: one block after the other. */
-template <bool PROF, typename LDS, bool RUN = false>
+/* PRE (with RUN): the execute stage behind the entropy pre-pass.  A block whose mark the pre-pass set takes its literals and
+ * its sequences from its slots instead of walking the Huffman and FSE bitstreams; its tables are still built here, block
+ * after block, so what a later unmarked block refers to and what the carry receives are the serial decoder's by
+ * construction.  A mark counts only if the definers the pre-pass used are the ones this wave arrived at itself. */
+template <bool PROF, typename LDS, bool RUN = false, bool PRE = false>
 static __device__ __forceinline__ void
 zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream_bytes, const u64 *__restrict__ rec_off,
 	      const u32 *__restrict__ rec_len, u32 nrec, u8 *out_base, const u64 *__restrict__ out_off,
 	      u32 *__restrict__ out_len, u8 *__restrict__ litbuf, u32 *__restrict__ status,
 	      u32 *__restrict__ chk_expect, u32 *__restrict__ chk_valid, unsigned long long *prof, u8 *seqbuf, u64 seqcap,
 	      const ZBlock *__restrict__ blocks = nullptr, u32 nblk = 0, const ZRun *__restrict__ runs = nullptr,
-	      u64 out_bytes = 0, u8 *carry_base = nullptr)
+	      u64 out_bytes = 0, u8 *carry_base = nullptr, const u32 *__restrict__ pre_mark = nullptr,
+	      const u32 *__restrict__ pre_def = nullptr, const u8 *__restrict__ pre_slots = nullptr)
 {
 	const int lane = wv_lane();
 	u64 pc[PROF ? 8 : 1] = {0}, tq = ZT();
@@ -233,6 +257,9 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 	const u64 *pre_seq = pre_on ? zs_region(seqbuf, out_off[rec]) + zs_nhdr(cap) / 2 : nullptr;
 	const u32 pre_nhdr = pre_on ? zs_nhdr(cap) : 0;
 	u32 bi = 0; /* index of the block, counting every block of the frame */
+	/* PRE: this block's mark and index in the table; the block that last defined the Huffman / LL / OF / ML table */
+	u32 pmark = 0, pabs = 0, pd_huf = ZPRE_NONE, pd_ll = ZPRE_NONE, pd_of = ZPRE_NONE, pd_ml = ZPRE_NONE;
+	bool pre_take = false;
 	if constexpr (RUN) {
 		/* ---- what the frame's earlier runs left: repeat offsets, the Huffman table, the three FSE tables ---- */
 		if (!(run_flags & ZR_FIRST)) {
@@ -271,6 +298,10 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 			ip = (u32)B.src_off;
 			flen = ip + B.src_len;
 			block_max = B.block_max;
+			if constexpr (PRE) {
+				pabs = run_first + bi;
+				pmark = wv_readfirst(pre_mark[pabs]);
+			}
 		}
 		if (flen - ip < 3) {
 			stc = ZBAD();
@@ -463,6 +494,15 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 					lit_done = true;
 				} else {
 					pre_left = 0;
+				}
+				if constexpr (PRE) {
+					if ((pmark & ZPRE_LIT) &&
+					    (ltype == 2 || (pd_huf != ZPRE_NONE && wv_readfirst(pre_def[4 * (size_t)pabs]) == pd_huf))) {
+						lit = pre_slots + (size_t)pabs * Z_PRE_STRIDE;
+						lit_done = true;
+					}
+					if (ltype == 2)
+						pd_huf = pabs;
 				}
 				/* ---- blocks that follow with `treeless` literals: all their streams at once ----
 				 * The device encoder writes one tree per 128 KiB unit and up to 15 more blocks that
@@ -876,6 +916,20 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 				  (L.misc[ZM_A + 2] & 0xC0000000u) == 0x40000000u;
 			all_fit = nseq && L.misc[ZM_A] < 0x40000000u && L.misc[ZM_A + 1] < 0x40000000u &&
 				  L.misc[ZM_A + 2] < 0x40000000u;
+			if constexpr (PRE) {
+				const bool r_ll = L.misc[ZM_A] == 0xFFFFFFFFu, r_of = L.misc[ZM_A + 1] == 0xFFFFFFFFu,
+					   r_ml = L.misc[ZM_A + 2] == 0xFFFFFFFFu;
+				const u32 *pd = pre_def + 4 * (size_t)pabs;
+				pre_take = (pmark & ZPRE_SEQ) && nseq && nseq <= Z_PRE_SEQCAP(block_max) &&
+					  (!r_ll || (pd_ll != ZPRE_NONE && wv_readfirst(pd[1]) == pd_ll)) &&
+					  (!r_of || (pd_of != ZPRE_NONE && wv_readfirst(pd[2]) == pd_of)) &&
+					  (!r_ml || (pd_ml != ZPRE_NONE && wv_readfirst(pd[3]) == pd_ml));
+				if (nseq) {
+					pd_ll = r_ll ? pd_ll : pabs;
+					pd_of = r_of ? pd_of : pabs;
+					pd_ml = r_ml ? pd_ml : pabs;
+				}
+			}
 			}
 			const u32 unit_modes = all_fit ? 0xFCu : 0u; /* Symbol_Compression_Modes of the unit's other blocks */
 			u32 lpos = 0; /* literals consumed */
@@ -1118,6 +1172,10 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 					}
 				}
 				} /* !pseq */
+				if constexpr (PRE) {
+					if (pre_take)
+						pseq = (const u64 *)(pre_slots + (size_t)pabs * Z_PRE_STRIDE + Z_PRE_LIT);
+				}
 				const bool from_scr = sq_left != 0 || pseq != nullptr;
 				/* lanes 0 / 1 / 2 carry the LL / OF / ML state and decode their own code; the
 				 * loop below is wave-uniform (one LDS round trip per sequence): every lane reads
@@ -1482,6 +1540,554 @@ zmt_zstd_dec_run_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const Z
 					 status, nullptr, nullptr, nullptr, nullptr, 0, blocks, nblk, runs, out_bytes, carry);
 }
 
+/* ------------------------------------------------------------------ the entropy pre-pass of a block table
+ * gpumt_zstd_decompress_blocks_pre: a run is one chain on one wave only where the format makes it one -- repeat offsets and
+ * matches that read earlier output.  A block's Huffman literals and its FSE sequence bitstream depend on nothing earlier
+ * blocks produced, only on tables that some earlier block may have described.  Four launches on the caller's stream, none of
+ * which waits on another wave (the stream orders them):
+ *   classify  one lane per block: the block, literals-section and sequences-section headers -> ZPre
+ *   resolve   one wave per run: for every block, the nearest earlier block of the run (in this call) that describes the
+ *             Huffman / LL / OF / ML table it would use -> def
+ *   entropy   one wave per Compressed_Block of the whole table: builds the block's tables in LDS from its own description
+ *             or its definer's bytes, decodes the literals and the sequences (ll | ml << 18 | offset value << 36, the
+ *             packing of zstd_dec_seq.hip; repeat codes stay codes) into the block's slots -> mark
+ *   execute   zmt_zstd_dec_run_pre_kernel, one wave per run: zstd_dec_body<RUN, PRE>
+ * A mark is set only when everything the serial walk checks on the way was clean, with the serial decoder's own code for
+ * the tables and the same steps for the bitstreams; whatever is odd stays unmarked and is judged by the run kernel's code.
+ * The tables are device memory and the input may be hostile: every read is inside [stream, stream + stream_bytes + 256),
+ * every write inside the block's slots. */
+extern "C" __global__ void __launch_bounds__(256)
+zmt_zstd_pre_classify_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const ZBlock *__restrict__ blocks, u32 nblk,
+			     ZPre *__restrict__ pre, u32 *__restrict__ def, u32 *__restrict__ mark)
+{
+	const u32 i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= nblk)
+		return;
+	ZPre P = {0, 0, 0, 0, 0, 0, 0, 0};
+	const ZBlock B = blocks[i];
+	if (B.src_off <= stream_bytes && B.src_len <= stream_bytes - B.src_off && B.block_max <= Z_BLOCK_MAX && B.src_len >= 5) {
+		const u8 *h = stream + B.src_off;
+		const u32 bh = (u32)h[0] | (u32)h[1] << 8 | (u32)h[2] << 16;
+		const u32 bsize = bh >> 3;
+		if (((bh >> 1) & 3) == 2 && bsize <= B.block_max && bsize == B.src_len - 3) {
+			const u8 *d = h + 3;
+#define ZPB(k) ((k) < bsize ? (u32)d[k] : 0u) /* (a header that leaves the block fails its size check below) */
+			const u32 b0 = ZPB(0), ltype = b0 & 3, sf = (b0 >> 2) & 3;
+			u32 regen = 0, csz = 0, hl = 0, streams = 1, err = 0;
+			if (ltype < 2) {
+				if (sf == 0 || sf == 2) {
+					regen = b0 >> 3;
+					hl = 1;
+				} else if (sf == 1) {
+					regen = (b0 | ZPB(1) << 8) >> 4;
+					hl = 2;
+				} else {
+					regen = (b0 | ZPB(1) << 8 | ZPB(2) << 16) >> 4;
+					hl = 3;
+				}
+				csz = ltype == 0 ? regen : 1;
+			} else {
+				const u64 v = (u64)(b0 | ZPB(1) << 8 | ZPB(2) << 16 | ZPB(3) << 24) | (u64)ZPB(4) << 32;
+				if (sf < 2) {
+					regen = (u32)(v >> 4) & 1023;
+					csz = (u32)(v >> 14) & 1023;
+					streams = sf == 0 ? 1 : 4;
+					hl = 3;
+				} else if (sf == 2) {
+					regen = (u32)(v >> 4) & 16383;
+					csz = (u32)(v >> 18) & 16383;
+					streams = 4;
+					hl = 4;
+				} else {
+					regen = (u32)(v >> 4) & 262143;
+					csz = (u32)(v >> 22) & 262143;
+					streams = 4;
+					hl = 5;
+				}
+				if (regen == 0)
+					err = 1;
+			}
+			if (regen > B.block_max || hl + csz >= bsize)
+				err = 1; /* (== : no sequences section) */
+			if (!err) {
+				const u32 sq0 = hl + csz, avail = bsize - sq0 < 512 ? bsize - sq0 : 512;
+				u32 p = 1, nseq = ZPB(sq0), modes = 0;
+				if (nseq >= 128) {
+					if (nseq == 255) {
+						nseq = (ZPB(sq0 + 1) | ZPB(sq0 + 2) << 8) + 0x7F00;
+						p = 3;
+					} else {
+						nseq = ((nseq - 128) << 8) + ZPB(sq0 + 1);
+						p = 2;
+					}
+				}
+				if (p > avail)
+					err = 1;
+				if (!err && nseq) {
+					if (p >= avail)
+						err = 1;
+					modes = ZPB(sq0 + p);
+					p++;
+					if (modes & 3)
+						err = 1;
+				} else if (!err && p != bsize - sq0) {
+					err = 1; /* no sequences: the section is its count alone */
+				}
+				if (!err) {
+					P.ok = 1;
+					P.lit = ltype | streams << 2 | hl << 8;
+					P.regen = regen;
+					P.lcsz = csz;
+					P.sq0 = sq0;
+					P.nseq = nseq;
+					P.sqh = p | modes << 8;
+					P.bsize = bsize;
+				}
+			}
+#undef ZPB
+		}
+	}
+	pre[i] = P;
+	mark[i] = 0;
+	for (int k = 0; k < 4; k++)
+		def[4 * (size_t)i + k] = ZPRE_NONE;
+}
+
+/* lanes 0..3 = Huffman, LL, OF, ML: each walks the run's blocks in order and notes, per block, the last definer so far */
+extern "C" __global__ void __launch_bounds__(64)
+zmt_zstd_pre_resolve_kernel(const ZRun *__restrict__ runs, u32 nrun, u32 nblk, const ZPre *__restrict__ pre,
+			    u32 *__restrict__ def)
+{
+	const u32 r = blockIdx.x;
+	const int lane = wv_lane();
+	if (r >= nrun || lane >= 4)
+		return;
+	const ZRun R = runs[r];
+	if (R.first > nblk || R.count > nblk - R.first)
+		return;
+	u32 last = ZPRE_NONE;
+	for (u32 b = R.first; b < R.first + R.count; b++) {
+		const ZPre P = pre[b];
+		if (!P.ok)
+			continue; /* raw, RLE: no tables; unparseable: the run ends there */
+		if (lane == 0) {
+			if ((P.lit & 3) == 2)
+				last = b;
+			if ((P.lit & 3) >= 2)
+				def[4 * (size_t)b] = last;
+		} else if (P.nseq) {
+			if (((P.sqh >> (16 - 2 * lane)) & 3) != 3) /* modes << 8: LL at bits 14-15, OF 12-13, ML 10-11 */
+				last = b;
+			def[4 * (size_t)b + (u32)lane] = last;
+		}
+	}
+}
+
+/* the sequences-section header of block `P` at body `src`: the descriptions of the tables in `want` (bit t) go to
+ * L.norm[t] / L.misc[ZM_A + t] as in zstd_dec_body, L.misc[ZM_E] = where the bitstream starts.  Wave-uniform. */
+template <typename LDS>
+static __device__ bool zpre_seq_header(LDS &L, const u8 *src, const ZPre &P, u32 want, const u8 *mem_lo, const u8 *mem_hi,
+				       int lane)
+{
+	wv_sync();
+	stage_load(L.stage, src, (long)P.sq0, 512, 0, mem_lo, mem_hi, lane);
+	wv_sync();
+	if (lane == 0) {
+		const u8 *d = L.stage;
+		const u32 avail = P.bsize - P.sq0 < 512 ? P.bsize - P.sq0 : 512, modes = P.sqh >> 8;
+		u32 p = P.sqh & 255, err = 0;
+		for (int t = 0; t < 3 && !err; t++) {
+			const int mode = (modes >> (6 - 2 * t)) & 3;
+			const int max_sym = t == 0 ? 36 : t == 1 ? 32 : 53, max_log = t == 1 ? 8 : 9;
+			u32 spec = 0xFFFFFFFFu;
+			if (mode == 0) {
+				if ((want >> t) & 1) {
+					const short *df = t == 0 ? Z_LL_DEF : t == 1 ? Z_OF_DEF : Z_ML_DEF;
+					const int n = t == 0 ? 36 : t == 1 ? 29 : 53;
+					for (int i = 0; i < n; i++)
+						L.norm[t][i] = df[i];
+					spec = (u32)n | (u32)(t == 1 ? 5 : 6) << 8 | 0x40000000u;
+				}
+			} else if (mode == 1) {
+				if (p >= avail || d[p] >= max_sym)
+					err = 1;
+				else
+					spec = 0x80000000u | d[p++];
+			} else if (mode == 2) {
+				int nsym = 0, lg = 0;
+				const int used = fse_read_ncount(d + p, avail - p, L.norm[t], max_sym, max_log, &nsym, &lg);
+				if (used < 0) {
+					err = 1;
+				} else {
+					p += (u32)used;
+					spec = (u32)nsym | (u32)lg << 8;
+				}
+			}
+			if ((want >> t) & 1)
+				L.misc[ZM_A + t] = spec;
+		}
+		L.misc[ZM_ERR] = err;
+		L.misc[ZM_E] = p;
+	}
+	wv_sync();
+	return L.misc[ZM_ERR] == 0;
+}
+
+extern "C" __global__ void __launch_bounds__(64)
+zmt_zstd_pre_entropy_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const ZBlock *__restrict__ blocks, u32 nblk,
+			    const ZPre *__restrict__ pre, const u32 *__restrict__ def, u8 *__restrict__ slots,
+			    u32 *__restrict__ mark)
+{
+	__shared__ __attribute__((aligned(16))) ZLds L;
+	const int lane = wv_lane();
+	const u32 b = blockIdx.x;
+	if (lane < 36)
+		L.llx[lane] = Z_LL_BASE[lane] | (u32)Z_LL_BITS[lane] << 24;
+	if (lane < 53)
+		L.mlx[lane] = Z_ML_BASE[lane] | (u32)Z_ML_BITS[lane] << 24;
+	if (b >= nblk)
+		return;
+	const ZPre P = pre[b];
+	const ZBlock B = blocks[b];
+	if (!P.ok || B.src_off > stream_bytes || B.src_len > stream_bytes - B.src_off || P.bsize != B.src_len - 3 ||
+	    B.block_max > Z_BLOCK_MAX || P.regen > B.block_max)
+		return; /* (the mark is 0 since the classify kernel) */
+	const u8 *mem_lo = stream, *mem_hi = stream + stream_bytes + 256;
+	const u8 *src = stream + B.src_off + 3;
+	const u32 bsize = P.bsize, regen = P.regen, lcsz = P.lcsz;
+	const u32 ltype = P.lit & 3, nstreams = (P.lit >> 2) & 7, lhl = P.lit >> 8;
+	u8 *lit_slot = slots + (size_t)b * Z_PRE_STRIDE;
+	u64 *seq_slot = (u64 *)(lit_slot + Z_PRE_LIT);
+	u32 m = 0;
+
+	/* ================= literals ================= */
+	if (ltype < 2) {
+		m |= ZPRE_LIT; /* raw: read in place; RLE: a fill -- both stay with the execute stage */
+	} else {
+		/* the tree: this block's, or (treeless) the one its definer describes */
+		const u32 tb = ltype == 2 ? b : def[4 * (size_t)b];
+		bool ok = tb <= b; /* (ZPRE_NONE is above every index) */
+		ZPre T = P;
+		const u8 *tsrc = src;
+		if (ok && tb != b) {
+			T = pre[tb];
+			const ZBlock TB = blocks[tb];
+			ok = T.ok && (T.lit & 3) == 2 && TB.src_off <= stream_bytes && TB.src_len <= stream_bytes - TB.src_off &&
+			     T.bsize == TB.src_len - 3;
+			tsrc = stream + TB.src_off + 3;
+		}
+		int huf_log = 0;
+		u32 tree = 0;
+		if (ok) {
+			const u32 thl = T.lit >> 8;
+			wv_sync();
+			stage_load(L.stage, tsrc, 0, 256, 0, mem_lo, mem_hi, lane);
+			wv_sync();
+			if (lane == 0) {
+				const u8 *d = L.stage;
+				const u32 avail = T.lcsz < 256 - thl ? T.lcsz : 256 - thl;
+				int nw = 0, lg = 0;
+				const int used = huf_read_weights(d + thl, avail, L.w, &nw, &lg, (u32 *)L.sq[0], L.norm[0], L.next[0]);
+				L.misc[ZM_ERR] = used < 0 || lg > 11;
+				L.misc[ZM_F] = used < 0 ? 0u : (u32)used;
+				L.misc[ZM_G] = (u32)nw;
+				L.misc[ZM_H] = (u32)lg;
+			}
+			wv_sync();
+			ok = L.misc[ZM_ERR] == 0;
+		}
+		if (ok) {
+			huf_log = (int)L.misc[ZM_H];
+			tree = ltype == 2 ? L.misc[ZM_F] : 0u;
+			for (u32 i = (u32)lane; i < (1u << 11); i += 64)
+				L.huf[i] = 0;
+			wv_sync();
+			huf_fill(L.huf, L.w, (int)L.misc[ZM_G], huf_log, lane);
+			wv_sync();
+			ok = lcsz >= tree + (nstreams == 4 ? 10u : 1u);
+		}
+		/* ---- Huffman streams: lane s < nstreams decodes stream s (the walk of zstd_dec_body) ---- */
+		const u32 body = lhl + tree;
+		u32 s_off = body, s_len = lcsz - tree, s_n = regen, s_dst = 0;
+		if (ok && nstreams == 4) {
+			const u32 j1 = uld16(src + body), j2 = uld16(src + body + 2), j3 = uld16(src + body + 4);
+			const u32 tot = lcsz - tree - 6, q = (regen + 3) / 4;
+			if (j1 + j2 + j3 >= tot || 3 * q > regen) {
+				ok = false;
+			} else {
+				const u32 sl = lane & 3;
+				s_off = body + 6 + (sl > 0 ? j1 : 0) + (sl > 1 ? j2 : 0) + (sl > 2 ? j3 : 0);
+				s_len = sl == 0 ? j1 : sl == 1 ? j2 : sl == 2 ? j3 : tot - j1 - j2 - j3;
+				s_n = sl < 3 ? q : regen - 3 * q;
+				s_dst = sl * q;
+			}
+		}
+		if (ok) {
+			const bool dec = (u32)lane < nstreams;
+			bool bad = false;
+			long pos = 0;
+			if (dec) {
+				const u32 lastb = s_len ? src[s_off + s_len - 1] : 0;
+				if (s_len == 0 || lastb == 0)
+					bad = true;
+				else
+					pos = 8 * (long)(s_len - 1) + hb32(lastb);
+			}
+			u32 done = 0;
+			while (!wv_any(dec && bad) && wv_any(dec && done < s_n)) {
+				wv_sync();
+				{
+					const int sg = lane >> 4;
+					const u32 g_off = wv_shfl(s_off, sg);
+					const u32 g_poslo = wv_shfl((u32)pos, sg);
+					const u32 g_poshi = wv_shfl((u32)((u64)pos >> 32), sg);
+					const long g_pos = (long)((u64)g_poshi << 32 | g_poslo);
+					const long whi = (g_pos + 7) >> 3;
+					if ((u32)sg < nstreams) {
+						const u32 o = 16u * ((u32)lane & 15);
+						const long rel = whi - 256 + (long)o;
+						const u8 *p = src + g_off + rel;
+						u64 a = 0, c = 0;
+						if (rel >= 0 && p + 16 <= mem_hi) {
+							a = ld64u(p);
+							c = ld64u(p + 8);
+						} else {
+							for (int k = 0; k < 8; k++) {
+								if (rel + k >= 0 && p + k < mem_hi)
+									a |= (u64)p[k] << (8 * k);
+								if (rel + 8 + k >= 0 && p + 8 + k < mem_hi)
+									c |= (u64)p[8 + k] << (8 * k);
+							}
+						}
+						u8 *w = L.stage + 256u * (u32)sg + o;
+						*(u64 *)w = a;
+						*(u64 *)(w + 8) = c;
+					}
+				}
+				wv_sync();
+				if (dec && done < s_n) {
+					const u8 *win = L.stage + 256u * (u32)lane;
+					const long wlo = ((pos + 7) >> 3) - 256;
+					const u32 todo = s_n - done < 128 ? s_n - done : 128;
+					u8 *dst = lit_slot + s_dst + done;
+					const int lg = huf_log;
+					const u32 hm = (1u << lg) - 1;
+					int ipos = (int)pos;
+					const int iwlo = (int)wlo;
+					u32 i = 0;
+					for (; i + 8 <= todo && ipos >= 0; i += 8) {
+						u64 acc = 0;
+						ZMT_UNROLL
+						for (int hlf = 0; hlf < 2; hlf++) {
+							const int tb2 = (ipos - 1) >> 3;
+							const u64 word = ld64u(win + (tb2 - 7 - iwlo));
+							int cb = ipos - 8 * (tb2 - 7);
+							ZMT_UNROLL
+							for (int k = 0; k < 4; k++) {
+								const u32 e = L.huf[(u32)(word >> (cb - lg)) & hm];
+								cb -= (int)(e >> 8);
+								acc |= (u64)(e & 255) << (8 * (4 * hlf + k));
+							}
+							ipos = cb + 8 * (tb2 - 7);
+						}
+						st64g(dst + i, acc);
+					}
+					{
+						u64 c = 0;
+						int cb = 0;
+						for (; i < todo && ipos >= 0; i++) {
+							if (cb < lg) {
+								const int tb2 = (ipos - 1) >> 3;
+								c = ld64u(win + (tb2 - 7 - iwlo));
+								cb = ipos - 8 * (tb2 - 7);
+							}
+							const u32 e = L.huf[(u32)(c >> (cb - lg)) & hm];
+							const int nb = (int)(e >> 8);
+							cb -= nb;
+							ipos -= nb;
+							dst[i] = (u8)e;
+						}
+					}
+					if (ipos < 0)
+						bad = true;
+					pos = ipos;
+					done += todo;
+					if (!bad && done == s_n && pos != 0)
+						bad = true;
+				}
+			}
+			if (!wv_any(dec && bad))
+				m |= ZPRE_LIT;
+		}
+	}
+
+	/* ================= sequences ================= */
+	const u32 nseq = P.nseq;
+	if (nseq == 0) {
+		m |= ZPRE_SEQ; /* nothing to decode */
+	} else if (nseq <= Z_PRE_SEQCAP(B.block_max)) {
+		const u32 modes = P.sqh >> 8;
+		/* where each table comes from */
+		u32 from[3];
+		bool ok = true;
+		for (int t = 0; t < 3; t++) {
+			from[t] = ((modes >> (6 - 2 * t)) & 3) == 3 ? def[4 * (size_t)b + 1 + t] : b;
+			if (from[t] > b) {
+				ok = false;
+			} else if (from[t] != b) {
+				const ZPre D = pre[from[t]];
+				const ZBlock DB = blocks[from[t]];
+				if (!D.ok || D.nseq == 0 || (((D.sqh >> 8) >> (6 - 2 * t)) & 3) == 3 || DB.src_off > stream_bytes ||
+				    DB.src_len > stream_bytes - DB.src_off || D.bsize != DB.src_len - 3)
+					ok = false;
+			}
+		}
+		int my_tab_log = 0;
+		u32 sq_hdr = 0;
+		/* this block first (its header also says where the bitstream starts), then the definers it names */
+		for (int k = 0; k < 4 && ok; k++) {
+			const u32 sb = k == 0 ? b : from[k - 1];
+			u32 want = 0;
+			for (int t = 0; t < 3; t++)
+				if (from[t] == sb)
+					want |= 1u << t;
+			if (k > 0 && (sb == b || (k > 1 && from[0] == sb) || (k > 2 && from[1] == sb)))
+				continue; /* built already */
+			if (k > 0 && !want)
+				continue;
+			const ZPre D = k == 0 ? P : pre[sb];
+			ok = zpre_seq_header(L, stream + blocks[sb].src_off + 3, D, want, mem_lo, mem_hi, lane);
+			if (!ok)
+				break;
+			if (k == 0)
+				sq_hdr = L.misc[ZM_E];
+			bool terr = false;
+			if (lane < 3 && ((want >> lane) & 1)) {
+				const u32 spec = L.misc[ZM_A + lane];
+				u32 *cells = lane == 0 ? L.ll : lane == 1 ? L.of : L.ml;
+				if (spec == 0xFFFFFFFFu) {
+					terr = true;
+				} else if (spec & 0x80000000u) {
+					const u32 sy = spec & 255;
+					cells[0] = sy | (lane == 1 ? sy : (lane == 0 ? L.llx[sy] : L.mlx[sy]) >> 24) << 10;
+					my_tab_log = 0;
+				} else {
+					const int lg = (int)((spec >> 8) & 255);
+					terr = lg > (lane == 1 ? 8 : 9) ||
+					       fse_build(cells, L.norm[lane], (int)(spec & 255), lg, L.next[lane],
+							 lane == 0 ? L.llx : lane == 2 ? L.mlx : (const u32 *)nullptr, lane) != 0;
+					my_tab_log = lg;
+				}
+			}
+			wv_sync();
+			if (wv_any(terr))
+				ok = false;
+		}
+		const u32 bs_off = P.sq0 + sq_hdr;
+		long pos = 0;
+		if (ok && bs_off >= bsize)
+			ok = false;
+		if (ok) {
+			const u32 bs_len = bsize - bs_off;
+			const u32 lastb = uld8(src + bs_off + bs_len - 1);
+			if (lastb == 0)
+				ok = false;
+			else
+				pos = 8 * (long)(bs_len - 1) + hb32(lastb);
+		}
+		if (ok) {
+			const int ll_log = (int)wv_readlane((u32)my_tab_log, 0), of_log = (int)wv_readlane((u32)my_tab_log, 1),
+				  ml_log = (int)wv_readlane((u32)my_tab_log, 2);
+			const u32 *mytab = lane == 1 ? L.of : lane == 2 ? L.ml : L.ll;
+			u64 *myval = L.sq[lane < 3 ? lane : 0];
+			const u32 e_of = lane == 1 ? 0u : ~0u, e_ml = lane == 0 ? ~0u : 0u;
+			const u32 s_ll = lane == 0 ? 0u : ~0u, s_ml = lane == 1 ? ~0u : 0u;
+			u32 state = 0;
+			for (u32 sbase = 0; sbase < nseq && ok; sbase += 64) {
+				const u32 k = nseq - sbase < 64 ? nseq - sbase : 64;
+				const long whi = (pos + 7) >> 3, wlo = whi - (long)Z_STAGE;
+				wv_sync();
+				stage_load(L.stage, src + bs_off, wlo, Z_STAGE, -(long)(bs_off + 16), mem_lo, mem_hi, lane);
+				wv_sync();
+				const u8 *win = L.stage - wlo;
+				if (sbase == 0) {
+					if (pos < (long)(ll_log + of_log + ml_log)) {
+						ok = false;
+						break;
+					}
+					const long tb = (pos - 1) >> 3;
+					const u64 w0 = ld64u(win + tb - 7), w1 = ld64u(win + tb - 15);
+					const u32 skip = (u32)(8 * (tb + 1) - pos);
+					state = xbits(w0, w1, skip + (lane == 0 ? 0u : lane == 1 ? (u32)ll_log : (u32)(ll_log + of_log)),
+						      (u32)(lane < 3 ? my_tab_log : 0));
+					pos -= ll_log + of_log + ml_log;
+				}
+				int bp = (int)pos;
+				const u8 *winb = win - 15;
+				for (u32 i = 0; i < k; i++) {
+					const int tb = (bp - 1) >> 3;
+					u64 w1 = 0, w0 = 0;
+					if (lane < 3) {
+						w1 = ld64u(winb + tb);
+						w0 = ld64u(winb + tb + 8);
+					}
+					const u32 cell = mytab[state];
+					const u32 skip = (u32)(8 * (tb + 1) - bp);
+					const u32 nb = sbase + i + 1 == nseq ? 0u : ZC_NB(cell), ab = ZC_AB(cell);
+					const u32 pk = ab | nb << 8;
+					const u32 p_ll = wv_readlane(pk, 0), p_of = wv_readlane(pk, 1), p_ml = wv_readlane(pk, 2);
+					const u32 a_ll = p_ll & 255, n_ll = p_ll >> 8, a_of = p_of & 255, n_of = p_of >> 8;
+					const u32 a_ml = p_ml & 255, n_ml = p_ml >> 8;
+					const u32 base3 = skip + a_of + a_ml + a_ll;
+					const u32 eo = skip + (a_of & e_of) + (a_ml & e_ml);
+					const u32 so = base3 + (n_ll & s_ll) + (n_ml & s_ml);
+					const u32 extra = xbits(w0, w1, eo, ab);
+					const u32 sbits = xbits(w0, w1, so, nb);
+					if (lane < 3)
+						myval[i] = (u64)extra | (u64)ZC_SYM(cell) << 32;
+					state = lane < 3 ? ZC_BASE(cell) + sbits : 0;
+					bp -= (int)(base3 - skip + n_ll + n_ml + n_of);
+				}
+				pos = bp;
+				if (pos < 0 || (sbase + k == nseq && pos != 0)) {
+					ok = false;
+					break;
+				}
+				wv_sync();
+				bool fit = true;
+				if ((u32)lane < k) {
+					const u64 q_ll = L.sq[0][lane], q_of = L.sq[1][lane], q_ml = L.sq[2][lane];
+					const u32 c_of = (u32)(q_of >> 32);
+					const u32 ll = (L.llx[(u32)(q_ll >> 32)] & 0xFFFFFFu) + (u32)q_ll;
+					const u32 ml = (L.mlx[(u32)(q_ml >> 32)] & 0xFFFFFFu) + (u32)q_ml;
+					/* offset codes above 27 do not fit the packing (and above 31 are an error): left to the block itself */
+					fit = c_of <= 27;
+					const u32 ofv = fit ? (1u << c_of) + (u32)q_of : 0u;
+					seq_slot[sbase + (u32)lane] = (u64)ll | (u64)ml << 18 | (u64)ofv << 36;
+				}
+				if (wv_any(!fit))
+					ok = false;
+			}
+			if (ok)
+				m |= ZPRE_SEQ;
+		}
+	}
+	if (lane == 0)
+		mark[b] = m;
+}
+
+extern "C" __global__ void __launch_bounds__(64)
+zmt_zstd_dec_run_pre_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const ZBlock *__restrict__ blocks, u32 nblk,
+			    const ZRun *__restrict__ runs, u32 nrun, u8 *out_base, u64 out_bytes, u8 *carry,
+			    u32 *__restrict__ run_len, u32 *__restrict__ status, u8 *__restrict__ litbuf,
+			    const u32 *__restrict__ mark, const u32 *__restrict__ def, const u8 *__restrict__ slots)
+{
+	__shared__ __attribute__((aligned(16))) ZLds L;
+	zstd_dec_body<false, ZLds, true, true>(L, 0u, stream, stream_bytes, nullptr, nullptr, nrun, out_base, nullptr, run_len,
+					       litbuf, status, nullptr, nullptr, nullptr, nullptr, 0, blocks, nblk, runs, out_bytes,
+					       carry, mark, def, slots);
+}
+
 /* ------------------------------------------------------------------ XXH64 content checksum
  * Four lanes per record = the four accumulators of XXH64 (one 32-byte stripe per step); only records
  * that carry a checksum do any work. */
@@ -1767,6 +2373,65 @@ int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stre
 		return GPUMT_E_ARG;
 	emu_zstd_decompress_blocks((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
 				   out_bytes, (u8 *)d_carry, d_run_len, d_status);
+	return GPUMT_OK;
+}
+
+/* pre_on = 0: the serial kernel, every mark 0 (the developer knob of the real boundary) */
+void emu_zstd_decompress_blocks_pre(const u8 *stream, u64 stream_bytes, const void *blocks, u32 nblk, const void *runs,
+				    u32 nrun, u8 *out, u64 out_bytes, u8 *carry, u32 *run_len, u32 *status, u32 *block_mark,
+				    int pre_on)
+{
+	std::vector<u32> markv((size_t)nblk + 1, 0xA5A5A5A5u);
+	if (!pre_on || nblk == 0) {
+		emu_zstd_decompress_blocks(stream, stream_bytes, blocks, nblk, runs, nrun, out, out_bytes, carry, run_len, status);
+		for (u32 i = 0; block_mark && i < nblk; i++)
+			block_mark[i] = 0;
+		return;
+	}
+	std::vector<u8> lit((size_t)nrun * Z_RUN_LITSLOT, 0xA5), slots((size_t)nblk * Z_PRE_STRIDE, 0xA5);
+	std::vector<ZPre> prev(nblk);
+	std::vector<u32> defv((size_t)nblk * 4, 0xA5A5A5A5u);
+	u8 *litp = lit.data(), *slotp = slots.data();
+	ZPre *prep = prev.data();
+	u32 *defp = defv.data(), *markp = markv.data();
+	emu::launch(emu::dim3{(nblk + 255) / 256, 1, 1}, emu::dim3{256, 1, 1}, [=]() {
+		zmt_zstd_pre_classify_kernel(stream, stream_bytes, (const ZBlock *)blocks, nblk, prep, defp, markp);
+	});
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_zstd_pre_resolve_kernel((const ZRun *)runs, nrun, nblk, prep, defp); });
+	emu::launch(emu::dim3{nblk, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_zstd_pre_entropy_kernel(stream, stream_bytes, (const ZBlock *)blocks, nblk, prep, defp, slotp, markp);
+	});
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_zstd_dec_run_pre_kernel(stream, stream_bytes, (const ZBlock *)blocks, nblk, (const ZRun *)runs, nrun, out,
+					    out_bytes, carry, run_len, status, litp, markp, defp, slotp);
+	});
+	for (u32 i = 0; block_mark && i < nblk; i++)
+		block_mark[i] = markv[i];
+}
+
+int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const gpumt_zstd_block *d_blocks,
+				     size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun, void *d_out, size_t out_bytes,
+				     void *d_carry, uint32_t *d_run_len, uint32_t *d_status, uint32_t *d_block_mark, int s)
+{
+	static_assert(GPUMT_ZSTD_PRE_SCRATCH(Z_BLOCK_MAX) == Z_PRE_STRIDE && sizeof(ZPre) == 32, "table layout");
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_stream || !d_blocks || !d_runs || !d_out || !d_carry || !d_run_len ||
+	    !d_status || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX || stream_bytes > 0xFFFFFFF0u)
+		return GPUMT_E_ARG;
+	/* (the emulated boundary keeps no variants: the environment alone, read once and validated as gpumt_open does) */
+	static int pre_on = -1;
+	if (pre_on < 0) {
+		const char *e = getenv("GPUMT_ZSTD_RUN_PRE");
+		pre_on = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				pre_on = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PRE=%s ignored (0 or 1)\n", e);
+		}
+	}
+	emu_zstd_decompress_blocks_pre((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
+				       out_bytes, (u8 *)d_carry, d_run_len, d_status, d_block_mark, pre_on);
 	return GPUMT_OK;
 }
 

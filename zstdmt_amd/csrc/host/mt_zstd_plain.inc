@@ -11,6 +11,12 @@
  * of the next batch's output, device to device, for the matches that reach back.  So host memory is about two batches of
  * input plus one block, device memory two batches of output plus a window, whatever the frame's size, and a frame's size
  * has no limit (its totals are 64-bit here).
+ * Under GPUMT_ZSTD_RUN_PRE=1, in front of the runs the device decodes the Huffman literals and the FSE sequences of all blocks of the batch side by side
+ * (gpumt_zstd_decompress_blocks_pre), which leaves a run's wave the table building and the sequence execution.  That takes
+ * GPUMT_ZSTD_PRE_SCRATCH(128 KiB) = 384 KiB of device scratch per block of the largest batch so far -- three times a
+ * batch's output for a frame of full blocks, more where blocks are smaller, up to 3 GiB for 8192 blocks -- inside the device
+ * boundary; where the device cannot give it, or the boundary
+ * has no such call, the batch decodes with the serial call, same bytes and verdicts.
  * Every plain frame takes this path, not only those larger than a batch: one walker and one decoder for plain input.
  * The content checksum is one serial XXH64 chain over the frame; its state lives on the device, is continued batch by
  * batch (gpumt_xxh64_carry) on stream ZP_XS and is settled when the batch's buffers are taken again, so it runs under
@@ -25,6 +31,7 @@
  * boundary that does not provide them (the plain-C one of the ThreadSanitizer runs, which only ever feeds records) still
  * links, and this path then fails with compression_library -- an error, not another way to decode. */
 extern __typeof__(gpumt_zstd_decompress_blocks) gpumt_zstd_decompress_blocks __attribute__((weak));
+extern __typeof__(gpumt_zstd_decompress_blocks_pre) gpumt_zstd_decompress_blocks_pre __attribute__((weak));
 extern __typeof__(gpumt_xxh64_carry) gpumt_xxh64_carry __attribute__((weak));
 extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
 
@@ -40,7 +47,8 @@ extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
 #define ZP_OFF_STATUS (ZP_OFF_RUNLEN + 4 * ZP_MAXB)
 #define ZP_OFF_DIGEST (ZP_OFF_STATUS + 4 * ZP_MAXB)
 #define ZP_OFF_VERDICT (ZP_OFF_DIGEST + 4 * ZP_MAXB)
-#define ZP_META_BYTES (ZP_OFF_VERDICT + 4 * ZP_MAXB + 64)
+#define ZP_OFF_MARK (ZP_OFF_VERDICT + 4 * ZP_MAXB) /* the pre-pass's verdict per block: read back under GPUMT_TRACE only */
+#define ZP_META_BYTES (ZP_OFF_MARK + 4 * ZP_MAXB + 64)
 #define ZP_AT(type, meta, dev, off) ((type *)((uint8_t *)((dev) ? (meta)->d : (meta)->h) + (off)))
 
 struct zp_frame { /* the frame the walker is inside of */
@@ -108,7 +116,12 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 	void *d_carry = NULL;
 	const uint8_t *hist_src = NULL; /* device: the end of the open frame's output so far */
 	double t_read = 0, t_dec = 0, t_hist = 0, t_back = 0, t_write = 0, t_chk = 0, t0;
-	size_t nbatch = 0, nblocks = 0, nruns = 0;
+	size_t nbatch = 0, nblocks = 0, nruns = 0, npre_seq = 0, npre_lit = 0;
+
+	/* The entropy stage is asked for with GPUMT_ZSTD_RUN_PRE=1 and otherwise off: its rate against the serial call has not
+	 * been measured on a device (profiles/plain_zst_blocks.txt), and it takes three launches and its scratch per batch. */
+	const char *pre_env = getenv("GPUMT_ZSTD_RUN_PRE");
+	const int use_pre = gpumt_zstd_decompress_blocks_pre && pre_env && pre_env[0] == '1' && !pre_env[1];
 
 	memset(&fr, 0, sizeof fr);
 	if (!gpumt_zstd_decompress_blocks || !gpumt_xxh64_carry || !gpumt_memcpy_d2d) {
@@ -403,10 +416,23 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 				rc |= gpumt_memcpy_h2d(g, s->in.d, s->in.h, in_bytes, 0);
 				rc |= gpumt_memcpy_h2d(g, ZP_AT(void, &s->meta, 1, ZP_OFF_BLOCKS), blocks, nblk * sizeof *blocks, 0);
 				rc |= gpumt_memcpy_h2d(g, ZP_AT(void, &s->meta, 1, ZP_OFF_RUNS), runs, nrun * sizeof *runs, 0);
-				rc |= gpumt_zstd_decompress_blocks(g, s->in.d, in_bytes, ZP_AT(gpumt_zstd_block, &s->meta, 1, ZP_OFF_BLOCKS),
-								   nblk, ZP_AT(gpumt_zstd_run, &s->meta, 1, ZP_OFF_RUNS), nrun, s->out.d,
-								   out_bytes, d_carry, ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_RUNLEN),
-								   ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_STATUS), 0);
+				if (use_pre) {
+					rc |= gpumt_zstd_decompress_blocks_pre(g, s->in.d, in_bytes,
+									       ZP_AT(gpumt_zstd_block, &s->meta, 1, ZP_OFF_BLOCKS), nblk,
+									       ZP_AT(gpumt_zstd_run, &s->meta, 1, ZP_OFF_RUNS), nrun, s->out.d,
+									       out_bytes, d_carry, ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_RUNLEN),
+									       ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_STATUS),
+									       ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_MARK), 0);
+					if (ctx->gpus.trace)
+						rc |= gpumt_memcpy_d2h(g, ZP_AT(void, &s->meta, 0, ZP_OFF_MARK), ZP_AT(void, &s->meta, 1, ZP_OFF_MARK),
+								       nblk * 4, 0);
+				} else {
+					rc |= gpumt_zstd_decompress_blocks(g, s->in.d, in_bytes,
+									   ZP_AT(gpumt_zstd_block, &s->meta, 1, ZP_OFF_BLOCKS), nblk,
+									   ZP_AT(gpumt_zstd_run, &s->meta, 1, ZP_OFF_RUNS), nrun, s->out.d, out_bytes,
+									   d_carry, ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_RUNLEN),
+									   ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_STATUS), 0);
+				}
 				rc |= gpumt_memcpy_d2h(g, run_len, ZP_AT(void, &s->meta, 1, ZP_OFF_RUNLEN), nrun * 4, 0);
 				rc |= gpumt_memcpy_d2h(g, status, ZP_AT(void, &s->meta, 1, ZP_OFF_STATUS), nrun * 4, 0);
 				rc |= gpumt_stream_sync(g, 0);
@@ -415,6 +441,12 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 					err = MTP(ERROR)(compression_library);
 					break;
 				}
+				if (ctx->gpus.trace && use_pre)
+					for (size_t k = 0; k < nblk; k++) {
+						const uint32_t mk = ZP_AT(uint32_t, &s->meta, 0, ZP_OFF_MARK)[k];
+						npre_seq += mk & 1;
+						npre_lit += (mk >> 1) & 1;
+					}
 				for (size_t r = 0; r < nrun && !err; r++)
 					if (status[r] != GPUMT_ST_OK)
 						err = zp_fail(status[r]);
@@ -506,6 +538,9 @@ out:
 			"[zstdmt plain] %zu batches, %zu blocks, %zu runs; read %.1f ms, history %.1f ms, h2d+decode %.1f ms, d2h %.1f ms, "
 			"write %.1f ms, waiting for the content checksum %.1f ms\n",
 			nbatch, nblocks, nruns, 1e3 * t_read, 1e3 * t_hist, 1e3 * t_dec, 1e3 * t_back, 1e3 * t_write, 1e3 * t_chk);
+	if (ctx->gpus.trace)
+		fprintf(stderr, "[zstdmt plain pre] %zu blocks: sequences of %zu and literals of %zu decoded ahead\n", nblocks,
+			npre_seq, npre_lit);
 	if (d_carry)
 		gpumt_free(g, d_carry);
 	if (d_states)
