@@ -223,6 +223,30 @@ int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t strea
 				const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
 				void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
 				uint32_t *d_status, int stream);
+/*
+ * The same call with the blocks of a linked run decoded side by side: same arguments, tables, statuses, d_block_len and
+ * d_run_len as gpumt_lz4_decompress_blocks (after an error in block k: the run's length is the sum of the blocks before k,
+ * d_block_len[k..] is not written, the status is that of the first failing block in block order; the bytes of d_out in
+ * [out_off + run_len, out_off + out_cap) are unspecified, nothing outside [out_off, out_off + out_cap) is written).
+ * Runs of one block -- every run of an independent-block frame -- are decoded by the same code as there.  Runs of two or
+ * more blocks take five stream-ordered launches, none of which waits on another wave: a plan (one wave), one wave per block
+ * that checks the table entry and the block checksum and walks the tokens without copying (decoded length, every verdict
+ * that does not depend on history), one wave per run that turns lengths into positions and finds the first failing block,
+ * one wave per block that decodes the block at its final position -- a match source below the block's first byte is not
+ * read; its distance before the block's start, 1..65535, goes into a u16 plane, one entry per output byte, and is copied
+ * along with the value by matches inside the block -- and one workgroup per run that fills those bytes in, block after
+ * block.  The runs of two or more blocks must name ascending, disjoint block ranges in run order (a linked frame's blocks
+ * in a batch are such a run); any other table is decoded by the serial code, with the same results.
+ * Internal scratch: GPUMT_LZ4_PAR_SCRATCH(out_bytes) + 20 bytes per block; when the device cannot provide it the call
+ * decodes serially rather than fail, keeps the scratch it has, and does not ask for that size again.
+ * GPUMT_LZ4_RUN_PAR=0 in the environment or gpumt_set_variant(h, "lz4_run_par", 0) make the call
+ * gpumt_lz4_decompress_blocks (1 turns it on again; other values are refused).
+ */
+#define GPUMT_LZ4_PAR_SCRATCH(out_bytes) (2 * (size_t)(out_bytes) + 8)
+int gpumt_lz4_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				    const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
+				    void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
+				    uint32_t *d_status, int stream);
 /* Ordered concatenation of what the runs decoded: d_pack_off[0..nrun] = exclusive scan of d_run_len and run r's bytes
  * moved from d_out + out_off to d_packed + d_pack_off[r] (d_packed_bytes: its size; must not overlap d_out). */
 int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
@@ -451,8 +475,8 @@ int gpumt_xxh32_batch(gpumt_ctx *h, const void *d_base, const uint64_t *d_off,
  * (gpumt_set_variant("lz4_dec", 2)). */
 int gpumt_debug_counters(gpumt_ctx *h, unsigned long long *dst, int n);
 
-/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre": 1 = default, 0 = off, anything else is refused
- * with -1 and changes nothing). Returns previous value. */
+/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre" and "lz4_run_par": 1 = default, 0 = off,
+ * anything else is refused with -1 and changes nothing). Returns previous value. */
 int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant);
 
 #ifdef __cplusplus

@@ -5,7 +5,7 @@ another on the same streams: the table of profiles/plain_lz4_blocks.txt.
   python tools/plain_lz4_bench.py --mib 1024 --runs 3 --old path/to/parent/libzstdmt_amd.so [--new path] [--out file]
 
 Every run is a process of its own (a library reads its batch size once; a fault ends one run, not the job) under a time
-limit; the two libraries alternate.  The callbacks copy 4 MiB per call, so the interpreter's share is a few hundred
+limit; the two libraries alternate (both see the caller's environment, GPUMT_LZ4_RUN_PAR included).  The callbacks copy 4 MiB per call, so the interpreter's share is a few hundred
 calls per GiB.  GPUMT_TRACE=1 is set for the new library: its per-stage times go into the output."""
 import argparse
 import ctypes as C
@@ -24,6 +24,7 @@ STREAMS = [  # name, liblz4_frame arguments
     ("4MiB_independent_checksum", dict(block_id=7, linked=0, checksum=1)),
     ("4MiB_linked_checksum", dict(block_id=7, linked=1, checksum=1)),
     ("64KiB_independent_checksum", dict(block_id=4, linked=0, checksum=1)),
+    ("64KiB_linked_checksum", dict(block_id=4, linked=1, checksum=1)),  # the LZ4F library default
 ]
 
 
@@ -115,7 +116,7 @@ def main():
                 rates[which].append(n / sec / 1e9)
                 say("%s run %d: %.3f s = %.3f GB/s  %s" % (which, r, sec, n / sec / 1e9, line.split()[-1]))
                 for t in p.stderr.splitlines():
-                    if "[lz4mt plain]" in t:
+                    if "[lz4mt plain" in t:
                         say("    " + t.strip())
         o, w = sorted(rates["old"]), sorted(rates["new"])
         say("=> old median %.3f GB/s (spread %.3f-%.3f), new median %.3f GB/s (spread %.3f-%.3f), new / old = %.2f"

@@ -38,6 +38,17 @@ __global__ void zmt_lz4_enc3_u32_kernel(const u8 *, u64, u32, u32, u32, u8 *, u6
 					unsigned long long *);
 __global__ void zmt_lz4_dec_serial(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *,
 				   u32 *, u32 *, u32 *, u32 *, u32);
+/* scratch of gpumt_lz4_decompress_blocks_par (lz4_dec_par.h) */
+struct Lz4Par {
+	u16 *origin;
+	u32 *owner, *mlen, *mst, *pos, *xst, *flag;
+};
+__global__ void zmt_lz4_par_plan_kernel(const gpumt_lz4_run *, u32, u32, u64, Lz4Par);
+__global__ void zmt_lz4_par_measure_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, Lz4Par);
+__global__ void zmt_lz4_par_scan_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u8 *, u64,
+					u32 *, u32 *, u32 *, Lz4Par);
+__global__ void zmt_lz4_par_exec_kernel(const u8 *, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u8 *, Lz4Par);
+__global__ void zmt_lz4_par_resolve_kernel(const gpumt_lz4_run *, u32, u32, u8 *, u64, u32 *, u32 *, u32 *, Lz4Par);
 __global__ void zmt_lz4_dec_blocks_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u8 *,
 					  u64, u32 *, u32 *, u32 *);
 __global__ void zmt_lz4_gather_runs_kernel(const u8 *, u64, const gpumt_lz4_run *, const u32 *, const u64 *, u32, u8 *,
@@ -134,6 +145,8 @@ struct gpumt_ctx {
 	int zseq_variant; /* 0 = sequence pre-pass (zstd_dec_seq.hip) in front of the frame decoder; 1 = none */
 	int zrun_pre;     /* 1 = entropy pre-pass in front of the block runs (gpumt_zstd_decompress_blocks_pre); 0 = none */
 	size_t zrun_pre_refused; /* the smallest pre-pass scratch the device has refused (0 = none yet): not asked for again */
+	int lrun_par;     /* 1 = linked runs of plain .lz4 blocks side by side (gpumt_lz4_decompress_blocks_par); 0 = one wave per run */
+	size_t lrun_par_refused; /* the smallest origin-plane scratch the device has refused (0 = none yet): not asked for again */
 	int sdec_variant; /* snappy decoder: 0 = element by element, 1 = 64 elements per batch (snappy.hip) */
 	int bdec_variant; /* brotli decoder: 0 = by batch size, 1 = the general kernel only, 2 = dec4 (four records per wave) + general for what it hands over */
 	int bdec_waves;   /* resident waves of the persistent brotli decoder kernel (whole device) */
@@ -294,6 +307,15 @@ int gpumt_open(int device, gpumt_ctx **out)
 				h->zrun_pre = e[0] - '0';
 			else
 				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PRE=%s ignored (0 or 1)\n", e);
+		}
+		/* GPUMT_LZ4_RUN_PAR=0: gpumt_lz4_decompress_blocks_par decodes every run with one wave */
+		e = getenv("GPUMT_LZ4_RUN_PAR");
+		h->lrun_par = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				h->lrun_par = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_LZ4_RUN_PAR=%s ignored (0 or 1)\n", e);
 		}
 		/* GPUMT_BROTLI_DEC: 0 = the batch size chooses (default), 1 = the general kernel, 2 = dec4 first */
 		e = getenv("GPUMT_BROTLI_DEC");
@@ -1028,6 +1050,69 @@ int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t strea
 	return GPUMT_OK;
 }
 
+int gpumt_lz4_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				    const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
+				    void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
+				    uint32_t *d_status, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_stream || !d_blocks || !d_runs || !d_out || !d_block_len || !d_run_len || !d_status ||
+	    nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	/* the origin plane (one u16 per byte of d_out) + five words per block + the plan's flag */
+	const size_t plane = (GPUMT_LZ4_PAR_SCRATCH(out_bytes) + 255) & ~(size_t)255;
+	const size_t need = (plane + nblk * 20 + 256 + 0xFFFFF) & ~(size_t)0xFFFFF;
+	/* a table without a run of two blocks (every frame of independent blocks) has nothing to decode side by side */
+	int par = h->lrun_par != 0 && nblk > nrun && !(h->lrun_par_refused && need >= h->lrun_par_refused);
+	if (par && need > h->scratch_bytes[1][s]) {
+		/* as gpumt_zstd_decompress_blocks_pre: the larger area first, a refused size is not asked for again */
+		void *p = dev_alloc(h, need);
+		if (!p) {
+			(void)hipGetLastError(); /* (a refused allocation is no error of this call) */
+			h->lrun_par_refused = need;
+			par = 0;
+		} else {
+			if (h->scratch[1][s]) {
+				if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+					dev_free(h, p);
+					return GPUMT_E_HIP;
+				}
+				dev_free(h, h->scratch[1][s]);
+			}
+			h->scratch[1][s] = p;
+			h->scratch_bytes[1][s] = need;
+		}
+	}
+	if (!par)
+		return gpumt_lz4_decompress_blocks(h, d_stream, stream_bytes, d_blocks, nblk, d_runs, nrun, d_out, out_bytes,
+						   d_block_len, d_run_len, d_status, s);
+	Lz4Par P;
+	P.origin = (u16 *)h->scratch[1][s];
+	P.owner = (u32 *)((u8 *)h->scratch[1][s] + plane);
+	P.mlen = P.owner + nblk;
+	P.mst = P.mlen + nblk;
+	P.pos = P.mst + nblk;
+	P.xst = P.pos + nblk;
+	P.flag = P.xst + nblk;
+	PROF0(11);
+	CK(hipMemsetAsync(P.owner, 0xFF, nblk * 4, h->st[s]));
+	CK(hipMemsetAsync(P.flag, 0, 4, h->st[s]));
+	hipLaunchKernelGGL(zmt_lz4_par_plan_kernel, dim3(1), dim3(64), 0, h->st[s], d_runs, (u32)nrun, (u32)nblk, (u64)out_bytes, P);
+	hipLaunchKernelGGL(zmt_lz4_par_measure_kernel, dim3((unsigned)nblk), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, P);
+	hipLaunchKernelGGL(zmt_lz4_par_scan_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out, (u64)out_bytes, d_block_len,
+			   d_run_len, d_status, P);
+	hipLaunchKernelGGL(zmt_lz4_par_exec_kernel, dim3((unsigned)nblk), dim3(64), 0, h->st[s], (const u8 *)d_stream, d_blocks,
+			   (u32)nblk, d_runs, (u8 *)d_out, P);
+	hipLaunchKernelGGL(zmt_lz4_par_resolve_kernel, dim3((unsigned)nrun), dim3(1024), 0, h->st[s], d_runs, (u32)nrun,
+			   (u32)nblk, (u8 *)d_out, (u64)out_bytes, d_block_len, d_run_len, d_status, P);
+	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
 int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
 			const uint32_t *d_run_len, size_t nrun, void *d_packed, size_t packed_bytes,
 			uint64_t *d_pack_off, int s)
@@ -1587,6 +1672,11 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 			return -1;
 		prev = h->zrun_pre;
 		h->zrun_pre = variant;
+	} else if (!strcmp(what, "lz4_run_par")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->lrun_par;
+		h->lrun_par = variant;
 	} else if (!strcmp(what, "snappy_dec")) {
 		prev = h->sdec_variant;
 		h->sdec_variant = variant;

@@ -237,19 +237,20 @@ struct Lz4Run { /* == gpumt_lz4_run */
 #define LZ4B_STORED 1u
 #define LZ4B_CHECKSUM 2u
 
-extern "C" __global__ void __launch_bounds__(64)
-zmt_lz4_dec_blocks_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const Lz4Block *__restrict__ blocks, u32 nblk,
-			  const Lz4Run *__restrict__ runs, u32 nrun, u8 *out_base, u64 out_bytes,
-			  u32 *__restrict__ blk_len, u32 *__restrict__ run_len, u32 *__restrict__ status)
+/* the checks of a run's table entry against the sizes the host passed */
+static __device__ __forceinline__ bool lz4_run_ok(const Lz4Run &R, u32 nblk, u64 out_bytes)
 {
-	const u32 r = blockIdx.x;
-	const int lane = wv_lane();
-	if (r >= nrun)
-		return;
-	const Lz4Run R = runs[r];
+	return !(R.first > nblk || R.count > nblk - R.first || R.low > R.out_off || R.out_off > out_bytes ||
+		 R.out_cap > out_bytes - R.out_off || R.out_off - R.low > 0x10000u || R.out_cap > 0xFFFE0000u);
+}
+
+/* one wave decodes run r, block after block */
+static __device__ void lz4_run_serial(const u8 *__restrict__ stream, u64 stream_bytes, const Lz4Block *__restrict__ blocks,
+				      u32 nblk, const Lz4Run &R, u32 r, u8 *out_base, u64 out_bytes, u32 *__restrict__ blk_len,
+				      u32 *__restrict__ run_len, u32 *__restrict__ status, int lane)
+{
 	u32 st = ST_OK, opos = 0, start = 0;
-	if (R.first > nblk || R.count > nblk - R.first || R.low > R.out_off || R.out_off > out_bytes ||
-	    R.out_cap > out_bytes - R.out_off || R.out_off - R.low > 0x10000u || R.out_cap > 0xFFFE0000u) {
+	if (!lz4_run_ok(R, nblk, out_bytes)) {
 		st = ST_BAD_RECORD;
 		goto done;
 	}
@@ -301,6 +302,18 @@ done:
 	}
 }
 
+extern "C" __global__ void __launch_bounds__(64)
+zmt_lz4_dec_blocks_kernel(const u8 *__restrict__ stream, u64 stream_bytes, const Lz4Block *__restrict__ blocks, u32 nblk,
+			  const Lz4Run *__restrict__ runs, u32 nrun, u8 *out_base, u64 out_bytes,
+			  u32 *__restrict__ blk_len, u32 *__restrict__ run_len, u32 *__restrict__ status)
+{
+	const u32 r = blockIdx.x;
+	if (r >= nrun)
+		return;
+	const Lz4Run R = runs[r];
+	lz4_run_serial(stream, stream_bytes, blocks, nblk, R, r, out_base, out_bytes, blk_len, run_len, status, wv_lane());
+}
+
 /* run r's decoded bytes (out_base + out_off, run_len[r] of them) -> dst + off[r]: the pack of the slots of
  * independent blocks that decoded to less than their capacity (off = zmt_scan_kernel over run_len); the pattern of
  * zmt_compact_kernel with a slot table in place of a stride */
@@ -324,12 +337,15 @@ zmt_lz4_gather_runs_kernel(const u8 *__restrict__ out_base, u64 out_bytes, const
 		d[(n & ~3u) + threadIdx.x] = s[(n & ~3u) + threadIdx.x];
 }
 
+#include "lz4_dec_par.h"
+
 #ifdef ZMT_EMU
 /*
  * TEST HARNESS ONLY (tests/emu compiles this file as host C++): the two device calls above over the fiber emulator,
  * with the shapes of include/gpumt.h, so that the host engine's plain .lz4 path runs on the CPU.  Synchronous, host
  * pointers stand in for device pointers; the same argument checks as gpumt.hip.  Never part of the product.
  */
+#include <vector>
 #include "../../../include/gpumt.h"
 extern "C" {
 void zmt_scan_kernel(const u32 *, u32, u64 *);
@@ -362,6 +378,56 @@ int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t strea
 		return GPUMT_E_ARG;
 	emu_lz4_decompress_blocks((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
 				  out_bytes, d_block_len, d_run_len, d_status);
+	return GPUMT_OK;
+}
+
+/* par_on = 0, or a table without a run of two blocks: the serial kernel (the developer knob of the real boundary) */
+void emu_lz4_decompress_blocks_par(const u8 *stream, u64 stream_bytes, const void *blocks, u32 nblk, const void *runs,
+				   u32 nrun, u8 *out, u64 out_bytes, u32 *blk_len, u32 *run_len, u32 *status, int par_on)
+{
+	if (!par_on || nblk <= nrun) {
+		emu_lz4_decompress_blocks(stream, stream_bytes, blocks, nblk, runs, nrun, out, out_bytes, blk_len, run_len, status);
+		return;
+	}
+	std::vector<u16> origin((size_t)out_bytes + 4, 0xA5A5); /* scratch starts as garbage */
+	std::vector<u32> owner(nblk, LZ4P_NONE), words((size_t)4 * nblk, 0xA5A5A5A5u), flag(1, 0);
+	const Lz4Par P = {origin.data(), owner.data(), words.data(), words.data() + nblk, words.data() + 2 * (size_t)nblk,
+			  words.data() + 3 * (size_t)nblk, flag.data()};
+	const Lz4Block *B = (const Lz4Block *)blocks;
+	const Lz4Run *R = (const Lz4Run *)runs;
+	emu::launch(emu::dim3{1, 1, 1}, emu::dim3{64, 1, 1}, [=]() { zmt_lz4_par_plan_kernel(R, nrun, nblk, out_bytes, P); });
+	emu::launch(emu::dim3{nblk, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_lz4_par_measure_kernel(stream, stream_bytes, B, nblk, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_lz4_par_scan_kernel(stream, stream_bytes, B, nblk, R, nrun, out, out_bytes, blk_len, run_len, status, P);
+	});
+	emu::launch(emu::dim3{nblk, 1, 1}, emu::dim3{64, 1, 1}, [=]() { zmt_lz4_par_exec_kernel(stream, B, nblk, R, out, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{LZ4P_RESOLVE_THREADS, 1, 1}, [=]() {
+		zmt_lz4_par_resolve_kernel(R, nrun, nblk, out, out_bytes, blk_len, run_len, status, P);
+	});
+}
+
+int gpumt_lz4_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const gpumt_lz4_block *d_blocks,
+				    size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun, void *d_out, size_t out_bytes,
+				    uint32_t *d_block_len, uint32_t *d_run_len, uint32_t *d_status, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_stream || !d_blocks || !d_runs || !d_out || !d_block_len || !d_run_len ||
+	    !d_status || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	/* (the emulated boundary keeps no variants: the environment alone, read once and validated as gpumt_open does) */
+	static int par_on = -1;
+	if (par_on < 0) {
+		const char *e = getenv("GPUMT_LZ4_RUN_PAR");
+		par_on = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				par_on = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_LZ4_RUN_PAR=%s ignored (0 or 1)\n", e);
+		}
+	}
+	emu_lz4_decompress_blocks_par((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
+				      out_bytes, d_block_len, d_run_len, d_status, par_on);
 	return GPUMT_OK;
 }
 

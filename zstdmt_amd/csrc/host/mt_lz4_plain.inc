@@ -5,8 +5,9 @@
  * work, the block is: a state machine walks the bytes read so far (frame header, block header, block body + block
  * checksum, end mark, content checksum; skippable frames in between are dropped), every block that is complete in the
  * buffer goes into the batch's block table, and the device decodes the table with gpumt_lz4_decompress_blocks --
- * independent blocks one wave each, the blocks of a linked frame in order by one wave, with the last 64 KiB of the
- * frame's earlier output copied in front of the batch's output.  Neither mode needs the whole frame: host memory is
+ * independent blocks one wave each, the blocks of a linked frame in order by one wave (or, under GPUMT_LZ4_RUN_PAR=1,
+ * side by side with gpumt_lz4_decompress_blocks_par), with the last 64 KiB of the frame's earlier output copied in
+ * front of the batch's output.  Neither mode needs the whole frame: host memory is
  * about two batches of input plus one block whatever the frame size, and there is no limit on a frame's size.
  * The content checksum is one serial XXH32 chain over the frame; its state lives on the device, is continued batch by
  * batch (gpumt_xxh32_carry) on stream PL_XS and is settled when the batch's buffers are taken again, so it runs under
@@ -22,6 +23,7 @@
  * linked with for ThreadSanitizer runs, which only ever feeds records) still links, and this path then fails with
  * compression_library -- an error, not another way to decode. */
 extern __typeof__(gpumt_lz4_decompress_blocks) gpumt_lz4_decompress_blocks __attribute__((weak));
+extern __typeof__(gpumt_lz4_decompress_blocks_par) gpumt_lz4_decompress_blocks_par __attribute__((weak));
 extern __typeof__(gpumt_lz4_pack_runs) gpumt_lz4_pack_runs __attribute__((weak));
 extern __typeof__(gpumt_xxh32_carry) gpumt_xxh32_carry __attribute__((weak));
 extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
@@ -29,6 +31,7 @@ extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
 #define PL_MAXB BATCH_MAXREC /* blocks, runs, frame segments of one batch */
 #define PL_HIST 65536u
 #define PL_XS 3 /* the stream of the carried content checksum */
+#define PL_PAR_DEFAULT 0 /* linked runs block-parallel unless GPUMT_LZ4_RUN_PAR says otherwise */
 
 /* the tables of a batch in the slot's `meta` buffer (pinned mirror and device copy alike) */
 #define PL_OFF_BLOCKS 0
@@ -122,6 +125,16 @@ static size_t lz4_plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_
 	dbuf pack = {0, 0, 0};
 	double t_read = 0, t_dec = 0, t_pack = 0, t_back = 0, t_write = 0, t_chk = 0, t0;
 	size_t nbatch = 0, npack = 0, nblocks = 0;
+
+	/* GPUMT_LZ4_RUN_PAR: 1 = the blocks of a linked run side by side (gpumt_lz4_decompress_blocks_par), 0 = one wave per
+	 * run; unset or any other value: PL_PAR_DEFAULT, as profiles/plain_lz4_blocks.txt decided it.  The call keeps an origin
+	 * plane of two bytes per byte of the batch's output inside the device boundary; where the device cannot give it, or
+	 * the boundary has no such call, the batch decodes with the serial call, same bytes and verdicts. */
+	const char *par_env = getenv("GPUMT_LZ4_RUN_PAR");
+	const int par_set = par_env && (par_env[0] == '0' || par_env[0] == '1') && !par_env[1];
+	__typeof__(gpumt_lz4_decompress_blocks) *const decode_blocks =
+		gpumt_lz4_decompress_blocks_par && (par_set ? par_env[0] == '1' : PL_PAR_DEFAULT) ? gpumt_lz4_decompress_blocks_par
+												      : gpumt_lz4_decompress_blocks;
 
 	memset(&fr, 0, sizeof fr);
 	if (!gpumt_lz4_decompress_blocks || !gpumt_lz4_pack_runs || !gpumt_xxh32_carry || !gpumt_memcpy_d2d) {
@@ -380,11 +393,10 @@ static size_t lz4_plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_
 					}
 					rc |= gpumt_memcpy_d2d(g, s->out.d, hist_src - hist, hist, 0);
 				}
-				rc |= gpumt_lz4_decompress_blocks(g, s->in.d, in_bytes, PL_AT(gpumt_lz4_block, &s->meta, 1, PL_OFF_BLOCKS),
-								  nblk, PL_AT(gpumt_lz4_run, &s->meta, 1, PL_OFF_RUNS), nrun, s->out.d,
-								  out_bytes, PL_AT(uint32_t, &s->meta, 1, PL_OFF_BLKLEN),
-								  PL_AT(uint32_t, &s->meta, 1, PL_OFF_RUNLEN),
-								  PL_AT(uint32_t, &s->meta, 1, PL_OFF_STATUS), 0);
+				rc |= decode_blocks(g, s->in.d, in_bytes, PL_AT(gpumt_lz4_block, &s->meta, 1, PL_OFF_BLOCKS), nblk,
+						    PL_AT(gpumt_lz4_run, &s->meta, 1, PL_OFF_RUNS), nrun, s->out.d, out_bytes,
+						    PL_AT(uint32_t, &s->meta, 1, PL_OFF_BLKLEN), PL_AT(uint32_t, &s->meta, 1, PL_OFF_RUNLEN),
+						    PL_AT(uint32_t, &s->meta, 1, PL_OFF_STATUS), 0);
 				rc |= gpumt_memcpy_d2h(g, run_len, PL_AT(void, &s->meta, 1, PL_OFF_RUNLEN), nrun * 4, 0);
 				rc |= gpumt_memcpy_d2h(g, status, PL_AT(void, &s->meta, 1, PL_OFF_STATUS), nrun * 4, 0);
 				rc |= gpumt_stream_sync(g, 0);
@@ -505,6 +517,9 @@ out:
 			"[lz4mt plain] %zu batches, %zu blocks, %zu packed; read %.1f ms, h2d+decode %.1f ms, pack %.1f ms, d2h %.1f ms, "
 			"write %.1f ms, waiting for the content checksum %.1f ms\n",
 			nbatch, nblocks, npack, 1e3 * t_read, 1e3 * t_dec, 1e3 * t_pack, 1e3 * t_back, 1e3 * t_write, 1e3 * t_chk);
+	if (ctx->gpus.trace)
+		fprintf(stderr, "[lz4mt plain par] linked runs %s\n",
+			decode_blocks != gpumt_lz4_decompress_blocks ? "block-parallel" : "one wave each");
 	dbuf_free(g, &pack);
 	if (d_states)
 		gpumt_free(g, d_states);

@@ -193,11 +193,12 @@ class Engine:
                                                    int(out_bytes), d_out_off.ptr, d_out_len.ptr,
                                                    d_status.ptr, stream), "lz4_decompress_batch")
 
-    def lz4_decompress_blocks(self, stream: bytes, blocks, runs, out_bytes, history=b"", pack=False):
+    def lz4_decompress_blocks(self, stream: bytes, blocks, runs, out_bytes, history=b"", pack=False, blk_fill=0,
+                              call="gpumt_lz4_decompress_blocks"):
         """gpumt_lz4_decompress_blocks over host bytes: `blocks` / `runs` are LZ4_BLOCK / LZ4_RUN arrays, `history` is
         placed at the start of the output (what a linked run reads behind its `low`).  -> (output area bytes,
         block_len[nblk], run_len[nrun], status[nrun]); with pack=True the output is what gpumt_lz4_pack_runs made of
-        the runs, in order."""
+        the runs, in order.  block_len starts as `blk_fill`: the words of blocks that were not decoded keep it."""
         blocks = np.ascontiguousarray(blocks, LZ4_BLOCK)
         runs = np.ascontiguousarray(runs, LZ4_RUN)
         nblk, nrun = len(blocks), len(runs)
@@ -205,12 +206,12 @@ class Engine:
         area[:len(history)] = np.frombuffer(history, np.uint8)
         d_stream = self.upload(stream, slack=0) if stream else self.alloc(64)
         d_blk, d_run, d_out = self.upload(blocks.view(np.uint8)), self.upload(runs.view(np.uint8)), self.upload(area, slack=0)
-        d_bl, d_rl, d_st = self.upload(np.zeros(nblk + 1, np.uint32)), self.alloc(nrun * 4), self.alloc(nrun * 4)
+        d_bl = self.upload(np.full(nblk + 1, blk_fill, np.uint32))
+        d_rl, d_st = self.alloc(nrun * 4), self.alloc(nrun * 4)
         d_pk, d_po = self.alloc(int(out_bytes) + 64), self.alloc((nrun + 1) * 8)
         try:
-            self._ck(self.L.gpumt_lz4_decompress_blocks(self.h, d_stream.ptr, len(stream), d_blk.ptr, nblk, d_run.ptr, nrun,
-                                                        d_out.ptr, int(out_bytes), d_bl.ptr, d_rl.ptr, d_st.ptr, 0),
-                     "lz4_decompress_blocks")
+            self._ck(getattr(self.L, call)(self.h, d_stream.ptr, len(stream), d_blk.ptr, nblk, d_run.ptr, nrun,
+                                           d_out.ptr, int(out_bytes), d_bl.ptr, d_rl.ptr, d_st.ptr, 0), call[6:])
             status = self.download(d_st, nrun * 4, np.uint32)
             run_len = self.download(d_rl, nrun * 4, np.uint32)
             blk_len = self.download(d_bl, nblk * 4, np.uint32)
@@ -226,6 +227,12 @@ class Engine:
             for b in (d_stream, d_blk, d_run, d_out, d_bl, d_rl, d_st, d_pk, d_po):
                 b.free()
         return out, blk_len, run_len, status
+
+    def lz4_decompress_blocks_par(self, stream: bytes, blocks, runs, out_bytes, history=b"", pack=False, blk_fill=0):
+        """gpumt_lz4_decompress_blocks_par, the same call with the blocks of a linked run decoded side by side: the
+        arguments and results of lz4_decompress_blocks"""
+        return self.lz4_decompress_blocks(stream, blocks, runs, out_bytes, history, pack, blk_fill,
+                                          call="gpumt_lz4_decompress_blocks_par")
 
     def xxh32_carry(self, data: bytes, pieces):
         """XXH32 of `data` continued over `pieces` (lengths that add up to len(data)), one gpumt_xxh32_carry call per piece
