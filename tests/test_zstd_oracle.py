@@ -118,3 +118,24 @@ def test_checksummed_and_unknown_size_frames():
             bad = bytearray(dst.raw[:n])
             bad[-1] ^= 1
             assert lib.zo_zstd_decompress_frame(bytes(bad), n, out, len(out), None) == H.SIZE_ERR
+
+
+def test_hand_built_frames():
+    """every case of tests/zstd_synth.py: the oracle decodes what libzstd 1.4.9 decoded (the recorded SHA-256, which the
+    generator held equal to the builder's content) and refuses what libzstd refused, and refuses the cases of
+    zstd_synth.DIVERGENT, which libzstd 1.4.9 accepts and RFC 8878 forbids (rep0 - 1 == 0 among them)"""
+    import zstd_synth as S
+    man = json.load(open(os.path.join(H.GOLDEN_DIR, "zstd_synth", "manifest.json")))
+    cs = S.families(man["seed"])
+    assert sorted(cs) == sorted(man["cases"])
+    bad = []
+    for name, e in sorted(cs.items()):
+        m = man["cases"][name]
+        assert S.sha256(e["frame"]) == m["frame_sha256"], name
+        got = H.oracle_zstdmt_decompress(S.record(e["frame"]), len(e["content"] or b"") + 4096)
+        if m["libzstd"] == "accept" and name not in S.DIVERGENT:
+            if got is None or H.sha256(got) != m["content_sha256"] or got != e["content"]:
+                bad.append((name, None if got is None else len(got)))
+        elif got is not None:
+            bad.append((name, "accepted"))
+    assert not bad, bad
