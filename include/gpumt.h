@@ -399,6 +399,35 @@ int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t 
 				     uint32_t *d_block_mark, int stream);
 
 /*
+ * The same call with, behind the entropy stage, a block-parallel execute stage: same arguments, contract, statuses,
+ * d_run_len, output bytes and carry as the two calls above -- a call of any of the three may follow a call of any other on
+ * the same carry.  d_block_mark is that of gpumt_zstd_decompress_blocks_pre.  Per run, the blocks behind its last
+ * Compressed_Block that is not fully marked (Raw, RLE and fully marked blocks) are its parallel suffix, the blocks in front
+ * its serial prefix; a suffix of fewer than 2 blocks leaves the run to the serial wave.  The prefix decodes as before on a
+ * scratch copy of the carry slot.  The suffix then takes stream-ordered launches, none of which waits on another wave:
+ * measure (one wave per block: decoded size and the block's repeat-offset transfer function), scan (one wave per run:
+ * positions, incoming repeat offsets, room), execute (one wave per block at its final position; a match source inside
+ * another suffix block is not read, its run position + 1 goes into a plane of one u32 per output byte and travels with
+ * copies inside the block), resolve (one workgroup per run, block after block, fills those bytes in) and carry (one wave
+ * per run: the tables from the last block that describes each).  A run that any stage refuses -- and every failing run --
+ * is decoded again by the serial wave from the caller's untouched carry slot, so its status, d_run_len, bytes and carry
+ * are the serial call's.  What stays serial per frame: the block-order resolve and the prefix.
+ * d_block_par (nblk words, may be NULL) receives 1 for every block whose bytes the parallel stage produced and kept.
+ * Internal scratch: that of gpumt_zstd_decompress_blocks_pre + GPUMT_ZSTD_PAR_SCRATCH(out_bytes) + 48 bytes per block +
+ * GPUMT_ZSTD_CARRY_BYTES + 84 bytes per run; when the device cannot provide it the call is
+ * gpumt_zstd_decompress_blocks_pre (d_block_par 0) and that size is not asked for again.
+ * The same holds for a table of more than 4096 runs (the pre call's own limit for its stage) and for a table without a run
+ * of two or more blocks: d_block_par is all 0 then.
+ * GPUMT_ZSTD_RUN_PAR=0 in the environment or gpumt_set_variant(h, "zstd_run_par", 0) turn the stage off the same way
+ * (1 turns it on again; other values are refused).
+ */
+#define GPUMT_ZSTD_PAR_SCRATCH(out_bytes) (4 * (size_t)(out_bytes) + 16)
+int gpumt_zstd_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				     const gpumt_zstd_block *d_blocks, size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun,
+				     void *d_out, size_t out_bytes, void *d_carry, uint32_t *d_run_len, uint32_t *d_status,
+				     uint32_t *d_block_mark, uint32_t *d_block_par, int stream);
+
+/*
  * XXH64 (seed 0) with carried state, the content checksum of a zstd frame decoded over several calls: gpumt_xxh32_carry's
  * contract with the same job record and flags, a state of GPUMT_XXH64_STATE_WORDS words per slot (four 64-bit
  * accumulators, the total length, up to 31 pending bytes), and `expect` / d_digest are the low 32 bits of the hash --
@@ -475,7 +504,7 @@ int gpumt_xxh32_batch(gpumt_ctx *h, const void *d_base, const uint64_t *d_off,
  * (gpumt_set_variant("lz4_dec", 2)). */
 int gpumt_debug_counters(gpumt_ctx *h, unsigned long long *dst, int n);
 
-/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre" and "lz4_run_par": 1 = default, 0 = off,
+/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre", "zstd_run_par" and "lz4_run_par": 1 = default, 0 = off,
  * anything else is refused with -1 and changes nothing). Returns previous value. */
 int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant);
 

@@ -6,6 +6,9 @@ another on the same streams: the tables of profiles/plain_zst_blocks.txt.
   python tools/plain_zst_bench.py --rss-mib 1024 --old ...      peak host RSS of one decode, either library
   python tools/plain_zst_bench.py --rle-blocks 16400            the hand-built frame of RLE blocks above 2 GiB (new only)
   python tools/plain_zst_bench.py --small-mib 256 --old ...     the same text as frames of 192 KiB, one behind the other
+  python tools/plain_zst_bench.py --stages --mib 256 --old ...  three legs per input instead of two: the old library with
+      nothing set (serial call) and under GPUMT_ZSTD_RUN_PRE=1 (pre call), the new one under GPUMT_ZSTD_RUN_PAR=1 (par call);
+      with --small-mib likewise
 
 Every run is a process of its own (a library reads its batch size once; a fault ends one run, not the job) under a time
 limit; the two libraries alternate.  The callbacks copy up to 128 KiB per call, the library's piece size.  GPUMT_TRACE=1
@@ -73,8 +76,12 @@ def one_run(libpath, path, nout, keep):
     return 0
 
 
-def child(a, libpath, path, n, keep, trace):
+def child(a, libpath, path, n, keep, trace, extra=None):
     env = dict(os.environ)
+    if extra is not None: # a leg of --stages: the two variables are the leg's own
+        env.pop("GPUMT_ZSTD_RUN_PRE", None)
+        env.pop("GPUMT_ZSTD_RUN_PAR", None)
+        env.update(extra)
     if trace:
         env["GPUMT_TRACE"] = "1"
     try:
@@ -95,6 +102,7 @@ def main():
     ap.add_argument("--rle-blocks", type=int, default=0)
     ap.add_argument("--small-mib", type=int, default=0)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--stages", action="store_true")
     ap.add_argument("--old", default=None)
     ap.add_argument("--new", default=os.path.join(ROOT, "zstdmt_amd", "lib", "libzstdmt_amd.so"))
     ap.add_argument("--out", default=None)
@@ -110,7 +118,11 @@ def main():
 
     def say(*x):
         print(*x, file=out, flush=True)
-    libs = ([("old", a.old)] if a.old else []) + [("new", a.new)]
+    libs = ([("old", a.old, None)] if a.old else []) + [("new", a.new, None)]
+    if a.stages:
+        assert a.old, "--stages compares against the parent's library"
+        libs = [("old_serial", a.old, {}), ("old_pre", a.old, {"GPUMT_ZSTD_RUN_PRE": "1"}),
+                ("new_par", a.new, {"GPUMT_ZSTD_RUN_PAR": "1"})]
     say("# old = %s\n# new = %s" % (a.old, a.new))
     if a.mib or a.small_mib:
         n = (a.mib or a.small_mib) << 20
@@ -118,7 +130,7 @@ def main():
         small = 192 << 10  # many frames side by side: 1.5 blocks each, every frame a run of its own
         say("# ZSTDCB_decompressDCtx, plain .zst, %s of %d MiB of the bench text, memcpy callbacks"
             % ("one frame" if a.mib else "frames of %d KiB" % (small >> 10), n >> 20))
-        say("# %d runs each, alternating old / new; GB/s of content" % a.runs)
+        say("# %d runs each, the legs alternating; GB/s of content" % a.runs)
         for name, kw in (STREAMS if a.mib else [("small_frames_level3", dict(level=3, checksum=0))]):
             path = os.path.join(a.tmp, "plain_%s.zst" % name)
             if a.mib:
@@ -128,10 +140,10 @@ def main():
             with open(path, "wb") as f:
                 f.write(fr)
             say("\n## %s: %d -> %d bytes" % (name, len(fr), n))
-            rates = {"old": [], "new": []}
+            rates = {which: [] for which, _, _ in libs}
             for r in range(a.runs):
-                for which, libpath in libs:
-                    sec, line, trace = child(a, libpath, path, n, True, which == "new")
+                for which, libpath, extra in libs:
+                    sec, line, trace = child(a, libpath, path, n, True, which.startswith("new"), extra)
                     if sec is None:
                         say("%s run %d: %s; the job ends here" % (which, r, line))
                         return 1
@@ -139,7 +151,7 @@ def main():
                     say("%s run %d: %.3f s = %.3f GB/s  %s" % (which, r, sec, n / sec / 1e9, " ".join(line.split()[2:])))
                     for t in trace:
                         say("    " + t)
-            for which, _ in libs:
+            for which, _, _ in libs:
                 v = sorted(rates[which])
                 say("=> %s median %.4f GB/s (spread %.4f-%.4f)" % (which, v[len(v) // 2], v[0], v[-1]))
             os.unlink(path)
@@ -151,8 +163,8 @@ def main():
             f.write(H.libzstd_frame(unit * (n // len(unit)), level=1, checksum=0))
         say("\n## peak host RSS, one frame of %d MiB (64 MiB of the bench text repeated, level 1), output counted, not kept"
             % a.rss_mib)
-        for which, libpath in libs:
-            sec, line, trace = child(a, libpath, path, n, False, which == "new")
+        for which, libpath, extra in libs:
+            sec, line, trace = child(a, libpath, path, n, False, which.startswith("new"), extra)
             say("%s: %s" % (which, line))
             for t in trace:
                 say("    " + t)

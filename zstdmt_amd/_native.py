@@ -66,6 +66,8 @@ GPUMT_SYMBOLS = {
     "gpumt_zstd_decompress_batch": (_i, [_vp, _vp, _sz, _u64p, _u32p, _sz, _vp, _sz, _u64p, _u32p, _u32p, _i]),
     "gpumt_zstd_decompress_blocks": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32p, _u32p, _i]),
     "gpumt_zstd_decompress_blocks_pre": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32p, _u32p, _u32p, _i]),
+    "gpumt_zstd_decompress_blocks_par": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32p, _u32p, _u32p, _u32p,
+                                              _i]),
     "gpumt_xxh64_carry": (_i, [_vp, _vp, _sz, _vp, _sz, _u32p, _u32p, _u32p, _i]),
     "gpumt_brotli_compress_batch": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i]),
     "gpumt_brotli_compress_batch_level": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i, _i]),

@@ -38,6 +38,28 @@ __global__ void zmt_lz4_enc3_u32_kernel(const u8 *, u64, u32, u32, u32, u8 *, u6
 					unsigned long long *);
 __global__ void zmt_lz4_dec_serial(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *,
 				   u32 *, u32 *, u32 *, u32 *, u32);
+/* scratch of gpumt_zstd_decompress_blocks_par (zstd_dec_par.h) */
+struct ZPar {
+	u32 *origin;
+	gpumt_zstd_run *prun;
+	u8 *pcarry;
+	u32 *sfx, *rflag, *plen, *pst, *rrep, *rlen, *rlast, *owner, *blen, *bst, *btf, *bpos, *brep, *xst, *flag;
+};
+__global__ void zmt_zstd_par_plan_kernel(const gpumt_zstd_run *, u32, u32, u64, ZPar);
+__global__ void zmt_zstd_par_split_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u64,
+					  const u32 *, ZPar);
+__global__ void zmt_zstd_par_prefix_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
+					   u64, const u8 *, u8 *, const u32 *, const u32 *, const u8 *, ZPar);
+__global__ void zmt_zstd_par_measure_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *,
+					    const void *, const u32 *, const u8 *, ZPar);
+__global__ void zmt_zstd_par_scan_kernel(const gpumt_zstd_run *, u32, ZPar);
+__global__ void zmt_zstd_par_exec_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, const void *,
+					 u8 *, u8 *, ZPar);
+__global__ void zmt_zstd_par_resolve_kernel(const gpumt_zstd_run *, u32, u8 *, ZPar);
+__global__ void zmt_zstd_par_fallback_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
+					     u64, u8 *, u32 *, u32 *, u8 *, const u32 *, const u32 *, const u8 *, ZPar);
+__global__ void zmt_zstd_par_carry_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32,
+					  const void *, u8 *, u32 *, u32 *, u32 *, ZPar);
 /* scratch of gpumt_lz4_decompress_blocks_par (lz4_dec_par.h) */
 struct Lz4Par {
 	u16 *origin;
@@ -98,7 +120,7 @@ __global__ void zmt_zstd_seq_kernel(const u8 *, u64, const u64 *, const u32 *, u
 __global__ void zmt_zstd_dec_run_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
 					u64, u8 *, u32 *, u32 *, u8 *);
 __global__ void zmt_zstd_pre_classify_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, void *, u32 *, u32 *);
-__global__ void zmt_zstd_pre_resolve_kernel(const gpumt_zstd_run *, u32, u32, const void *, u32 *);
+__global__ void zmt_zstd_pre_resolve_kernel(const gpumt_zstd_run *, u32, u32, const void *, u32 *, u32 *);
 __global__ void zmt_zstd_pre_entropy_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const void *, const u32 *, u8 *,
 					    u32 *);
 __global__ void zmt_zstd_dec_run_pre_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32, u8 *,
@@ -145,6 +167,8 @@ struct gpumt_ctx {
 	int zseq_variant; /* 0 = sequence pre-pass (zstd_dec_seq.hip) in front of the frame decoder; 1 = none */
 	int zrun_pre;     /* 1 = entropy pre-pass in front of the block runs (gpumt_zstd_decompress_blocks_pre); 0 = none */
 	size_t zrun_pre_refused; /* the smallest pre-pass scratch the device has refused (0 = none yet): not asked for again */
+	int zrun_par;     /* 1 = block-parallel execute stage behind it (gpumt_zstd_decompress_blocks_par); 0 = none */
+	size_t zrun_par_refused; /* the same for that stage's scratch */
 	int lrun_par;     /* 1 = linked runs of plain .lz4 blocks side by side (gpumt_lz4_decompress_blocks_par); 0 = one wave per run */
 	size_t lrun_par_refused; /* the smallest origin-plane scratch the device has refused (0 = none yet): not asked for again */
 	int sdec_variant; /* snappy decoder: 0 = element by element, 1 = 64 elements per batch (snappy.hip) */
@@ -307,6 +331,15 @@ int gpumt_open(int device, gpumt_ctx **out)
 				h->zrun_pre = e[0] - '0';
 			else
 				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PRE=%s ignored (0 or 1)\n", e);
+		}
+		/* GPUMT_ZSTD_RUN_PAR=0: gpumt_zstd_decompress_blocks_par decodes as gpumt_zstd_decompress_blocks_pre */
+		e = getenv("GPUMT_ZSTD_RUN_PAR");
+		h->zrun_par = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				h->zrun_par = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PAR=%s ignored (0 or 1)\n", e);
 		}
 		/* GPUMT_LZ4_RUN_PAR=0: gpumt_lz4_decompress_blocks_par decodes every run with one wave */
 		e = getenv("GPUMT_LZ4_RUN_PAR");
@@ -1405,7 +1438,7 @@ int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t 
 	hipLaunchKernelGGL(zmt_zstd_pre_classify_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, h->st[s],
 			   (const u8 *)d_stream, (u64)stream_bytes, d_blocks, (u32)nblk, pre, def, mark);
 	hipLaunchKernelGGL(zmt_zstd_pre_resolve_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], d_runs, (u32)nrun, (u32)nblk,
-			   (const void *)pre, def);
+			   (const void *)pre, def, (u32 *)nullptr);
 	hipLaunchKernelGGL(zmt_zstd_pre_entropy_kernel, dim3((unsigned)nblk), dim3(64), 0, h->st[s], (const u8 *)d_stream,
 			   (u64)stream_bytes, d_blocks, (u32)nblk, (const void *)pre, (const u32 *)def, slots, mark);
 	hipLaunchKernelGGL(zmt_zstd_dec_run_pre_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], (const u8 *)d_stream,
@@ -1413,6 +1446,113 @@ int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t 
 			   d_run_len, d_status, lit, (const u32 *)mark, (const u32 *)def, (const u8 *)slots);
 	if (d_block_mark)
 		CK(hipMemcpyAsync(d_block_mark, mark, nblk * 4, hipMemcpyDeviceToDevice, h->st[s]));
+	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+int gpumt_zstd_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				     const gpumt_zstd_block *d_blocks, size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun,
+				     void *d_out, size_t out_bytes, void *d_carry, uint32_t *d_run_len, uint32_t *d_status,
+				     uint32_t *d_block_mark, uint32_t *d_block_par, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_stream || !d_blocks || !d_runs || !d_out || !d_carry || !d_run_len || !d_status ||
+	    nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX || stream_bytes > 0xFFFFFFF0u)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	/* the pre-pass scratch, then the origin plane (one u32 per byte of d_out), a run record, a carry copy and 13 words per
+	 * run, 12 words per block */
+	const size_t lit_bytes = (nrun * (size_t)GPUMT_ZSTD_RUN_SCRATCH + 255) & ~(size_t)255;
+	const size_t pre_bytes = (nblk * (ZPRE_STRIDE + ZPRE_REC + 16 + 4) + 255) & ~(size_t)255;
+	const size_t plane = (GPUMT_ZSTD_PAR_SCRATCH(out_bytes) + 255) & ~(size_t)255;
+	const size_t run_bytes = (nrun * (sizeof(gpumt_zstd_run) + (size_t)GPUMT_ZSTD_CARRY_BYTES + 13 * 4) + 255) & ~(size_t)255;
+	const size_t need = (lit_bytes + pre_bytes + plane + run_bytes + nblk * 12 * 4 + 256 + 0xFFFFF) & ~(size_t)0xFFFFF;
+	/* a table without a run of two blocks has nothing to decode side by side */
+	int par = h->zrun_par != 0 && h->zrun_pre != 0 && nblk > nrun && nrun <= 4096 &&
+		  !(h->zrun_par_refused && need >= h->zrun_par_refused);
+	if (par && need > h->scratch_bytes[1][s]) {
+		/* as gpumt_zstd_decompress_blocks_pre: the larger area first, a refused size is not asked for again */
+		void *p = dev_alloc(h, need);
+		if (!p) {
+			(void)hipGetLastError(); /* (a refused allocation is no error of this call) */
+			h->zrun_par_refused = need;
+			par = 0;
+		} else {
+			if (h->scratch[1][s]) {
+				if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+					dev_free(h, p);
+					return GPUMT_E_HIP;
+				}
+				dev_free(h, h->scratch[1][s]);
+			}
+			h->scratch[1][s] = p;
+			h->scratch_bytes[1][s] = need;
+		}
+	}
+	if (!par) {
+		if (d_block_par && nblk)
+			CK(hipMemsetAsync(d_block_par, 0, nblk * 4, h->st[s]));
+		return gpumt_zstd_decompress_blocks_pre(h, d_stream, stream_bytes, d_blocks, nblk, d_runs, nrun, d_out, out_bytes,
+							d_carry, d_run_len, d_status, d_block_mark, s);
+	}
+	u8 *lit = (u8 *)h->scratch[1][s], *slots = lit + lit_bytes;
+	void *pre = slots + nblk * ZPRE_STRIDE;
+	u32 *def = (u32 *)((u8 *)pre + nblk * ZPRE_REC), *mark = def + 4 * nblk;
+	ZPar P;
+	P.origin = (u32 *)(lit + lit_bytes + pre_bytes);
+	P.prun = (gpumt_zstd_run *)((u8 *)P.origin + plane);
+	P.pcarry = (u8 *)(P.prun + nrun);
+	P.sfx = (u32 *)(P.pcarry + nrun * (size_t)GPUMT_ZSTD_CARRY_BYTES);
+	P.rflag = P.sfx + nrun;
+	P.plen = P.rflag + nrun;
+	P.pst = P.plen + nrun;
+	P.rrep = P.pst + nrun;
+	P.rlen = P.rrep + 3 * nrun;
+	P.rlast = P.rlen + nrun;
+	P.owner = (u32 *)((u8 *)P.prun + run_bytes);
+	P.blen = P.owner + nblk;
+	P.bst = P.blen + nblk;
+	P.btf = P.bst + nblk;
+	P.bpos = P.btf + 3 * nblk;
+	P.brep = P.bpos + nblk;
+	P.xst = P.brep + 3 * nblk;
+	u32 *par_out = P.xst + nblk; /* block_par, where the caller wants none */
+	P.flag = par_out + nblk;
+	if (d_block_par)
+		par_out = d_block_par;
+	const hipStream_t st = h->st[s];
+	const dim3 wave(64), per_run((unsigned)nrun), per_blk((unsigned)nblk);
+	const u8 *stream = (const u8 *)d_stream;
+	PROF0(11);
+	CK(hipMemsetAsync(P.owner, 0xFF, nblk * 4, st));
+	CK(hipMemsetAsync(P.flag, 0, 4, st));
+	CK(hipMemsetAsync(par_out, 0, nblk * 4, st));
+	hipLaunchKernelGGL(zmt_zstd_pre_classify_kernel, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, st, stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, pre, def, mark);
+	hipLaunchKernelGGL(zmt_zstd_pre_resolve_kernel, per_run, wave, 0, st, d_runs, (u32)nrun, (u32)nblk, (const void *)pre, def,
+			   P.rlast);
+	hipLaunchKernelGGL(zmt_zstd_pre_entropy_kernel, per_blk, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk,
+			   (const void *)pre, (const u32 *)def, slots, mark);
+	hipLaunchKernelGGL(zmt_zstd_par_plan_kernel, dim3(1), wave, 0, st, d_runs, (u32)nrun, (u32)nblk, (u64)out_bytes, P);
+	hipLaunchKernelGGL(zmt_zstd_par_split_kernel, per_run, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk, d_runs,
+			   (u32)nrun, (u64)out_bytes, (const u32 *)mark, P);
+	hipLaunchKernelGGL(zmt_zstd_par_prefix_kernel, per_run, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk, d_runs,
+			   (u32)nrun, (u8 *)d_out, (u64)out_bytes, (const u8 *)d_carry, lit, (const u32 *)mark, (const u32 *)def,
+			   (const u8 *)slots, P);
+	hipLaunchKernelGGL(zmt_zstd_par_measure_kernel, per_blk, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk, d_runs,
+			   (const void *)pre, (const u32 *)mark, (const u8 *)slots, P);
+	hipLaunchKernelGGL(zmt_zstd_par_scan_kernel, per_run, wave, 0, st, d_runs, (u32)nrun, P);
+	hipLaunchKernelGGL(zmt_zstd_par_exec_kernel, per_blk, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk, d_runs,
+			   (const void *)pre, slots, (u8 *)d_out, P);
+	hipLaunchKernelGGL(zmt_zstd_par_resolve_kernel, per_run, dim3(1024), 0, st, d_runs, (u32)nrun, (u8 *)d_out, P);
+	hipLaunchKernelGGL(zmt_zstd_par_fallback_kernel, per_run, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk,
+			   d_runs, (u32)nrun, (u8 *)d_out, (u64)out_bytes, (u8 *)d_carry, d_run_len, d_status, lit,
+			   (const u32 *)mark, (const u32 *)def, (const u8 *)slots, P);
+	hipLaunchKernelGGL(zmt_zstd_par_carry_kernel, per_run, wave, 0, st, stream, (u64)stream_bytes, d_blocks, (u32)nblk, d_runs,
+			   (u32)nrun, (const void *)pre, (u8 *)d_carry, d_run_len, d_status, par_out, P);
+	if (d_block_mark)
+		CK(hipMemcpyAsync(d_block_mark, mark, nblk * 4, hipMemcpyDeviceToDevice, st));
 	PROF1(11);
 	CK(hipGetLastError());
 	return GPUMT_OK;
@@ -1672,6 +1812,11 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 			return -1;
 		prev = h->zrun_pre;
 		h->zrun_pre = variant;
+	} else if (!strcmp(what, "zstd_run_par")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->zrun_par;
+		h->zrun_par = variant;
 	} else if (!strcmp(what, "lz4_run_par")) {
 		if (variant != 0 && variant != 1)
 			return -1;

@@ -124,6 +124,56 @@ static inline u32 zbad_(int line)
 		}                                                                                  \
 	} while (0)
 
+/* Repeat offsets of one batch of k <= 64 sequences, one per lane (RFC 8878 3.1.1.5): `off` arrives as offset value - 3 and
+ * leaves as the offset of the lane's sequence, rep0..2 as they stand behind the batch.  Runs of new offsets fold into the
+ * history in one step, only the sequences that use a repeat code are walked one by one.  True: a repeat code gave offset 0. */
+static __device__ __forceinline__ bool z_rep_fold(u32 ofv, u32 ll, bool act0, u32 k, u32 &rep0, u32 &rep1, u32 &rep2, u32 &off,
+						   int lane)
+{
+	u64 repm = wv_ballot(act0 && ofv <= 3);
+	u32 prev = 0;
+	bool rerr = false;
+	for (;;) {
+		const u32 j = repm ? (u32)wv_ffs(repm) - 1 : k;
+		const u32 m = j - prev;
+		if (m >= 1) {
+			const u32 o1 = wv_readlane(off, (int)(j - 1));
+			u32 n1, n2;
+			if (m >= 3) {
+				n1 = wv_readlane(off, (int)(j - 2));
+				n2 = wv_readlane(off, (int)(j - 3));
+			} else if (m == 2) {
+				n1 = wv_readlane(off, (int)(j - 2));
+				n2 = rep0;
+			} else {
+				n1 = rep0;
+				n2 = rep1;
+			}
+			rep2 = n2;
+			rep1 = n1;
+			rep0 = o1;
+		}
+		if (j >= k)
+			break;
+		const u32 idx = wv_readlane(ofv, (int)j) - 1 + (wv_readlane(ll, (int)j) == 0);
+		u32 o = rep0;
+		if (idx) {
+			o = idx == 1 ? rep1 : idx == 2 ? rep2 : rep0 - 1;
+			if (o == 0)
+				rerr = true;
+			if (idx > 1)
+				rep2 = rep1;
+			rep1 = rep0;
+			rep0 = o;
+		}
+		if ((u32)lane == j)
+			off = o;
+		repm &= repm - 1;
+		prev = j + 1;
+	}
+	return rerr;
+}
+
 /* RUN: the same decoder started at a block header instead of a frame header (zmt_zstd_dec_run_kernel, at the end of this
  * file): "record" rec is run rec of `runs`, its blocks are entries of `blocks`, out_len receives the run's length, and what
  * a frame's later blocks may refer to travels in a ZCarry.  No units and no pre-pass there: one block after the other. */
@@ -139,7 +189,7 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 	      u32 *__restrict__ chk_expect, u32 *__restrict__ chk_valid, unsigned long long *prof, u8 *seqbuf, u64 seqcap,
 	      const ZBlock *__restrict__ blocks = nullptr, u32 nblk = 0, const ZRun *__restrict__ runs = nullptr,
 	      u64 out_bytes = 0, u8 *carry_base = nullptr, const u32 *__restrict__ pre_mark = nullptr,
-	      const u32 *__restrict__ pre_def = nullptr, const u8 *__restrict__ pre_slots = nullptr)
+	      const u32 *__restrict__ pre_def = nullptr, const u8 *__restrict__ pre_slots = nullptr, bool carry_by_rec = false)
 {
 	const int lane = wv_lane();
 	u64 pc[PROF ? 8 : 1] = {0}, tq = ZT();
@@ -165,7 +215,8 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 		}
 		return;
 	}
-	ZCarry *cy = RUN ? (ZCarry *)(carry_base + (size_t)R.carry * sizeof(ZCarry)) : nullptr;
+	/* (carry_by_rec: the slot is the run's own copy in the scratch of gpumt_zstd_decompress_blocks_par, zstd_dec_par.h) */
+	ZCarry *cy = RUN ? (ZCarry *)(carry_base + (size_t)(carry_by_rec ? rec : R.carry) * sizeof(ZCarry)) : nullptr;
 	const u32 run_hist = R.hist, run_count = R.count, run_first = R.first, run_flags = R.flags;
 	if (!RUN && wv_readfirst(status[rec]) != want_status)
 		return; /* rejected by the probe kernel, or not this variant's record */
@@ -1274,52 +1325,9 @@ zstd_dec_body(LDS &L, u32 want_status, const u8 *__restrict__ stream, u64 stream
 					/* repeat offsets (RFC 8878 3.1.1.5): runs of new offsets fold into the history in
 					 * one step, only the sequences that use a repeat code are walked one by one */
 					u32 off = ofv - 3;
-					{
-						u64 repm = wv_ballot(act0 && ofv <= 3);
-						u32 prev = 0;
-						bool rerr = false;
-						for (;;) {
-							const u32 j = repm ? (u32)wv_ffs(repm) - 1 : k;
-							const u32 m = j - prev;
-							if (m >= 1) {
-								const u32 o1 = wv_readlane(off, (int)(j - 1));
-								u32 n1, n2;
-								if (m >= 3) {
-									n1 = wv_readlane(off, (int)(j - 2));
-									n2 = wv_readlane(off, (int)(j - 3));
-								} else if (m == 2) {
-									n1 = wv_readlane(off, (int)(j - 2));
-									n2 = rep0;
-								} else {
-									n1 = rep0;
-									n2 = rep1;
-								}
-								rep2 = n2;
-								rep1 = n1;
-								rep0 = o1;
-							}
-							if (j >= k)
-								break;
-							const u32 idx = wv_readlane(ofv, (int)j) - 1 + (wv_readlane(ll, (int)j) == 0);
-							u32 o = rep0;
-							if (idx) {
-								o = idx == 1 ? rep1 : idx == 2 ? rep2 : rep0 - 1;
-								if (o == 0)
-									rerr = true;
-								if (idx > 1)
-									rep2 = rep1;
-								rep1 = rep0;
-								rep0 = o;
-							}
-							if ((u32)lane == j)
-								off = o;
-							repm &= repm - 1;
-							prev = j + 1;
-						}
-						if (rerr) {
-							stc = ZBAD();
-							break;
-						}
+					if (z_rep_fold(ofv, ll, act0, k, rep0, rep1, rep2, off, lane)) {
+						stc = ZBAD();
+						break;
 					}
 					const u32 len = ll + ml;
 					const u32 incl = wv_scan_incl(len), lincl = wv_scan_incl(ll);
@@ -1656,7 +1664,7 @@ zmt_zstd_pre_classify_kernel(const u8 *__restrict__ stream, u64 stream_bytes, co
 /* lanes 0..3 = Huffman, LL, OF, ML: each walks the run's blocks in order and notes, per block, the last definer so far */
 extern "C" __global__ void __launch_bounds__(64)
 zmt_zstd_pre_resolve_kernel(const ZRun *__restrict__ runs, u32 nrun, u32 nblk, const ZPre *__restrict__ pre,
-			    u32 *__restrict__ def)
+			    u32 *__restrict__ def, u32 *__restrict__ run_last)
 {
 	const u32 r = blockIdx.x;
 	const int lane = wv_lane();
@@ -1681,6 +1689,8 @@ zmt_zstd_pre_resolve_kernel(const ZRun *__restrict__ runs, u32 nrun, u32 nblk, c
 			def[4 * (size_t)b + (u32)lane] = last;
 		}
 	}
+	if (run_last) /* the run's last definer of each table (the carry kernel of zstd_dec_par.h) */
+		run_last[4 * (size_t)r + (u32)lane] = last;
 }
 
 /* the sequences-section header of block `P` at body `src`: the descriptions of the tables in `want` (bit t) go to
@@ -2088,6 +2098,8 @@ zmt_zstd_dec_run_pre_kernel(const u8 *__restrict__ stream, u64 stream_bytes, con
 					       carry, mark, def, slots);
 }
 
+#include "zstd_dec_par.h"
+
 /* ------------------------------------------------------------------ XXH64 content checksum
  * Four lanes per record = the four accumulators of XXH64 (one 32-byte stripe per step); only records
  * that carry a checksum do any work. */
@@ -2398,7 +2410,7 @@ void emu_zstd_decompress_blocks_pre(const u8 *stream, u64 stream_bytes, const vo
 		zmt_zstd_pre_classify_kernel(stream, stream_bytes, (const ZBlock *)blocks, nblk, prep, defp, markp);
 	});
 	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1},
-		    [=]() { zmt_zstd_pre_resolve_kernel((const ZRun *)runs, nrun, nblk, prep, defp); });
+		    [=]() { zmt_zstd_pre_resolve_kernel((const ZRun *)runs, nrun, nblk, prep, defp, nullptr); });
 	emu::launch(emu::dim3{nblk, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
 		zmt_zstd_pre_entropy_kernel(stream, stream_bytes, (const ZBlock *)blocks, nblk, prep, defp, slotp, markp);
 	});
@@ -2432,6 +2444,118 @@ int gpumt_zstd_decompress_blocks_pre(gpumt_ctx *h, const void *d_stream, size_t 
 	}
 	emu_zstd_decompress_blocks_pre((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
 				       out_bytes, (u8 *)d_carry, d_run_len, d_status, d_block_mark, pre_on);
+	return GPUMT_OK;
+}
+
+/* par_on = 0: the pre call, every block_par 0 */
+void emu_zstd_decompress_blocks_par(const u8 *stream, u64 stream_bytes, const void *blocks_, u32 nblk, const void *runs_,
+				    u32 nrun, u8 *out, u64 out_bytes, u8 *carry, u32 *run_len, u32 *status, u32 *block_mark,
+				    u32 *block_par, int par_on)
+{
+	for (u32 i = 0; block_par && i < nblk; i++)
+		block_par[i] = 0;
+	if (!par_on || nblk == 0) {
+		emu_zstd_decompress_blocks_pre(stream, stream_bytes, blocks_, nblk, runs_, nrun, out, out_bytes, carry, run_len,
+					       status, block_mark, 1);
+		return;
+	}
+	const ZBlock *blocks = (const ZBlock *)blocks_;
+	const ZRun *runs = (const ZRun *)runs_;
+	std::vector<u8> lit((size_t)nrun * Z_RUN_LITSLOT, 0xA5), slots((size_t)nblk * Z_PRE_STRIDE, 0xA5);
+	std::vector<ZPre> prev(nblk);
+	std::vector<u32> defv((size_t)nblk * 4, 0xA5A5A5A5u), markv((size_t)nblk, 0xA5A5A5A5u), parv((size_t)nblk, 0);
+	std::vector<u32> origin((size_t)out_bytes + 4, 0xA5A5A5A5u), perrun((size_t)nrun * 13, 0xA5A5A5A5u),
+		perblk((size_t)nblk * 11 + 1, 0xA5A5A5A5u);
+	std::vector<ZRun> prun(nrun);
+	std::vector<u8> pcarry((size_t)nrun * sizeof(ZCarry), 0xA5);
+	u8 *litp = lit.data(), *slotp = slots.data();
+	ZPre *prep = prev.data();
+	u32 *defp = defv.data(), *markp = markv.data(), *parp = parv.data();
+	ZPar P;
+	P.origin = origin.data();
+	P.prun = prun.data();
+	P.pcarry = pcarry.data();
+	P.sfx = perrun.data();
+	P.rflag = P.sfx + nrun;
+	P.plen = P.rflag + nrun;
+	P.pst = P.plen + nrun;
+	P.rrep = P.pst + nrun;
+	P.rlen = P.rrep + 3 * (size_t)nrun;
+	P.rlast = P.rlen + nrun;
+	P.owner = perblk.data();
+	P.blen = P.owner + nblk;
+	P.bst = P.blen + nblk;
+	P.btf = P.bst + nblk;
+	P.bpos = P.btf + 3 * (size_t)nblk;
+	P.brep = P.bpos + nblk;
+	P.xst = P.brep + 3 * (size_t)nblk;
+	P.flag = P.xst + nblk;
+	for (u32 i = 0; i < nblk; i++)
+		P.owner[i] = ZPAR_NONE;
+	P.flag[0] = 0;
+	const emu::dim3 wave{64, 1, 1};
+	emu::launch(emu::dim3{(nblk + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_zstd_pre_classify_kernel(stream, stream_bytes, blocks, nblk, prep, defp, markp); });
+	emu::launch(emu::dim3{nrun, 1, 1}, wave, [=]() { zmt_zstd_pre_resolve_kernel(runs, nrun, nblk, prep, defp, P.rlast); });
+	emu::launch(emu::dim3{nblk, 1, 1}, wave,
+		    [=]() { zmt_zstd_pre_entropy_kernel(stream, stream_bytes, blocks, nblk, prep, defp, slotp, markp); });
+	emu::launch(emu::dim3{1, 1, 1}, wave, [=]() { zmt_zstd_par_plan_kernel(runs, nrun, nblk, out_bytes, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, wave,
+		    [=]() { zmt_zstd_par_split_kernel(stream, stream_bytes, blocks, nblk, runs, nrun, out_bytes, markp, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, wave, [=]() {
+		zmt_zstd_par_prefix_kernel(stream, stream_bytes, blocks, nblk, runs, nrun, out, out_bytes, carry, litp, markp, defp,
+					   slotp, P);
+	});
+	emu::launch(emu::dim3{nblk, 1, 1}, wave,
+		    [=]() { zmt_zstd_par_measure_kernel(stream, stream_bytes, blocks, nblk, runs, prep, markp, slotp, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, wave, [=]() { zmt_zstd_par_scan_kernel(runs, nrun, P); });
+	emu::launch(emu::dim3{nblk, 1, 1}, wave,
+		    [=]() { zmt_zstd_par_exec_kernel(stream, stream_bytes, blocks, nblk, runs, prep, slotp, out, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{ZPAR_RESOLVE_THREADS, 1, 1},
+		    [=]() { zmt_zstd_par_resolve_kernel(runs, nrun, out, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, wave, [=]() {
+		zmt_zstd_par_fallback_kernel(stream, stream_bytes, blocks, nblk, runs, nrun, out, out_bytes, carry, run_len, status,
+					     litp, markp, defp, slotp, P);
+	});
+	emu::launch(emu::dim3{nrun, 1, 1}, wave, [=]() {
+		zmt_zstd_par_carry_kernel(stream, stream_bytes, blocks, nblk, runs, nrun, prep, carry, run_len, status, parp, P);
+	});
+	for (u32 i = 0; i < nblk; i++) {
+		if (block_mark)
+			block_mark[i] = markv[i];
+		if (block_par)
+			block_par[i] = parv[i];
+	}
+}
+
+int gpumt_zstd_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const gpumt_zstd_block *d_blocks,
+				     size_t nblk, const gpumt_zstd_run *d_runs, size_t nrun, void *d_out, size_t out_bytes,
+				     void *d_carry, uint32_t *d_run_len, uint32_t *d_status, uint32_t *d_block_mark,
+				     uint32_t *d_block_par, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_stream || !d_blocks || !d_runs || !d_out || !d_carry || !d_run_len ||
+	    !d_status || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX || stream_bytes > 0xFFFFFFF0u)
+		return GPUMT_E_ARG;
+	/* (the environment alone, as the pre call above) */
+	static int par_on = -1;
+	if (par_on < 0) {
+		const char *e = getenv("GPUMT_ZSTD_RUN_PAR");
+		par_on = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				par_on = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PAR=%s ignored (0 or 1)\n", e);
+		}
+	}
+	if (!par_on) {
+		for (size_t i = 0; d_block_par && i < nblk; i++)
+			d_block_par[i] = 0;
+		return gpumt_zstd_decompress_blocks_pre(h, d_stream, stream_bytes, d_blocks, nblk, d_runs, nrun, d_out, out_bytes,
+							d_carry, d_run_len, d_status, d_block_mark, s);
+	}
+	emu_zstd_decompress_blocks_par((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
+				       out_bytes, (u8 *)d_carry, d_run_len, d_status, d_block_mark, d_block_par, 1);
 	return GPUMT_OK;
 }
 

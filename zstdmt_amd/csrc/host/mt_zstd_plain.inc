@@ -32,6 +32,7 @@
  * links, and this path then fails with compression_library -- an error, not another way to decode. */
 extern __typeof__(gpumt_zstd_decompress_blocks) gpumt_zstd_decompress_blocks __attribute__((weak));
 extern __typeof__(gpumt_zstd_decompress_blocks_pre) gpumt_zstd_decompress_blocks_pre __attribute__((weak));
+extern __typeof__(gpumt_zstd_decompress_blocks_par) gpumt_zstd_decompress_blocks_par __attribute__((weak));
 extern __typeof__(gpumt_xxh64_carry) gpumt_xxh64_carry __attribute__((weak));
 extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
 
@@ -122,6 +123,10 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 	 * been measured on a device (profiles/plain_zst_blocks.txt), and it takes three launches and its scratch per batch. */
 	const char *pre_env = getenv("GPUMT_ZSTD_RUN_PRE");
 	const int use_pre = gpumt_zstd_decompress_blocks_pre && pre_env && pre_env[0] == '1' && !pre_env[1];
+	/* The block-parallel execute stage behind it (gpumt_zstd_decompress_blocks_par) likewise, under GPUMT_ZSTD_RUN_PAR=1
+	 * only: whether it becomes the default is decided from profiles/plain_zst_blocks.txt. */
+	const char *par_env = getenv("GPUMT_ZSTD_RUN_PAR");
+	const int use_par = gpumt_zstd_decompress_blocks_par && par_env && par_env[0] == '1' && !par_env[1];
 
 	memset(&fr, 0, sizeof fr);
 	if (!gpumt_zstd_decompress_blocks || !gpumt_xxh64_carry || !gpumt_memcpy_d2d) {
@@ -416,7 +421,17 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 				rc |= gpumt_memcpy_h2d(g, s->in.d, s->in.h, in_bytes, 0);
 				rc |= gpumt_memcpy_h2d(g, ZP_AT(void, &s->meta, 1, ZP_OFF_BLOCKS), blocks, nblk * sizeof *blocks, 0);
 				rc |= gpumt_memcpy_h2d(g, ZP_AT(void, &s->meta, 1, ZP_OFF_RUNS), runs, nrun * sizeof *runs, 0);
-				if (use_pre) {
+				if (use_par) {
+					rc |= gpumt_zstd_decompress_blocks_par(g, s->in.d, in_bytes,
+									       ZP_AT(gpumt_zstd_block, &s->meta, 1, ZP_OFF_BLOCKS), nblk,
+									       ZP_AT(gpumt_zstd_run, &s->meta, 1, ZP_OFF_RUNS), nrun, s->out.d,
+									       out_bytes, d_carry, ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_RUNLEN),
+									       ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_STATUS),
+									       ZP_AT(uint32_t, &s->meta, 1, ZP_OFF_MARK), NULL, 0);
+					if (ctx->gpus.trace)
+						rc |= gpumt_memcpy_d2h(g, ZP_AT(void, &s->meta, 0, ZP_OFF_MARK), ZP_AT(void, &s->meta, 1, ZP_OFF_MARK),
+								       nblk * 4, 0);
+				} else if (use_pre) {
 					rc |= gpumt_zstd_decompress_blocks_pre(g, s->in.d, in_bytes,
 									       ZP_AT(gpumt_zstd_block, &s->meta, 1, ZP_OFF_BLOCKS), nblk,
 									       ZP_AT(gpumt_zstd_run, &s->meta, 1, ZP_OFF_RUNS), nrun, s->out.d,
@@ -441,7 +456,7 @@ static size_t plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_t *f
 					err = MTP(ERROR)(compression_library);
 					break;
 				}
-				if (ctx->gpus.trace && use_pre)
+				if (ctx->gpus.trace && (use_pre || use_par))
 					for (size_t k = 0; k < nblk; k++) {
 						const uint32_t mk = ZP_AT(uint32_t, &s->meta, 0, ZP_OFF_MARK)[k];
 						npre_seq += mk & 1;

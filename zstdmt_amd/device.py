@@ -314,6 +314,36 @@ class Engine:
         assert (raw[int(out_bytes):] == 0xCC).all(), "decoder wrote past the end of its output"
         return raw[:int(out_bytes)].tobytes(), run_len, status, cy_out, mark
 
+    def zstd_decompress_blocks_par(self, stream: bytes, blocks, runs, out_bytes, history=b"", carry=None):
+        """gpumt_zstd_decompress_blocks_par, the same call with the block-parallel execute stage behind the entropy
+        pre-pass, with zstd_decompress_blocks's arguments -> (output area bytes, run_len[nrun], status[nrun], carry bytes,
+        mark[nblk], par[nblk])"""
+        blocks = np.ascontiguousarray(blocks, ZSTD_BLOCK)
+        runs = np.ascontiguousarray(runs, ZSTD_RUN)
+        nblk, nrun = len(blocks), len(runs)
+        area = np.full(int(out_bytes) + 64, 0xCC, np.uint8)
+        area[:len(history)] = np.frombuffer(history, np.uint8)
+        cy = np.full(2 * ZSTD_CARRY_BYTES, 0xA5, np.uint8) if carry is None else np.frombuffer(carry, np.uint8)
+        d_stream = self.upload(stream) if stream else self.alloc(320)
+        d_blk, d_run, d_out = self.upload(blocks.view(np.uint8)), self.upload(runs.view(np.uint8)), self.upload(area, slack=0)
+        d_cy, d_rl, d_st = self.upload(cy), self.alloc(nrun * 4), self.alloc(nrun * 4)
+        d_mk, d_pr = self.alloc(max(nblk, 1) * 4), self.alloc(max(nblk, 1) * 4)
+        try:
+            self._ck(self.L.gpumt_zstd_decompress_blocks_par(self.h, d_stream.ptr, len(stream), d_blk.ptr, nblk, d_run.ptr,
+                                                             nrun, d_out.ptr, int(out_bytes), d_cy.ptr, d_rl.ptr, d_st.ptr,
+                                                             d_mk.ptr, d_pr.ptr, 0), "zstd_decompress_blocks_par")
+            status = self.download(d_st, nrun * 4, np.uint32)
+            run_len = self.download(d_rl, nrun * 4, np.uint32)
+            mark = self.download(d_mk, nblk * 4, np.uint32) if nblk else np.zeros(0, np.uint32)
+            par = self.download(d_pr, nblk * 4, np.uint32) if nblk else np.zeros(0, np.uint32)
+            raw = self.download(d_out, int(out_bytes) + 64)
+            cy_out = self.download(d_cy, 2 * ZSTD_CARRY_BYTES).tobytes()
+        finally:
+            for b in (d_stream, d_blk, d_run, d_out, d_cy, d_rl, d_st, d_mk, d_pr):
+                b.free()
+        assert (raw[int(out_bytes):] == 0xCC).all(), "decoder wrote past the end of its output"
+        return raw[:int(out_bytes)].tobytes(), run_len, status, cy_out, mark, par
+
     def xxh64_carry(self, data: bytes, pieces):
         """low 32 bits of XXH64 of `data` continued over `pieces` (lengths that add up to len(data)), one gpumt_xxh64_carry
         call per piece with the state carried on the device -> digest"""
