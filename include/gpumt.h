@@ -247,6 +247,35 @@ int gpumt_lz4_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t s
 				    const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
 				    void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
 				    uint32_t *d_status, int stream);
+/*
+ * The same call with every block cut into segments that are decoded side by side: same arguments, tables, statuses,
+ * d_block_len, d_run_len and error contract as gpumt_lz4_decompress_blocks_par, for linked runs and for independent blocks
+ * (runs of one block) alike.  A segment is a stretch of one block's sequences that starts at a token: the first one whose
+ * output position is at or behind k x seg_bytes (a stored block is cut at k x seg_bytes), so a block has at most
+ * ceil(decoded length / seg_bytes) segments and a sequence longer than a segment stays whole.  The five launches of
+ * gpumt_lz4_decompress_blocks_par with that unit: the plan also gives every block room for its cuts, the wave that measures
+ * a block writes the cuts (input and output position, block-relative) down, one wave per segment decodes it at its final
+ * position -- origins are distances before the segment's start; the end-of-block rules and the history check see the
+ * block's and the run's positions as the serial decoder does -- and one workgroup per run fills the origins in, segment
+ * after segment.  No wave waits on another wave of its launch.  Every run of one block or more must name ascending,
+ * disjoint block ranges in run order and the runs' areas must not overlap; any other table is decoded by the serial code.
+ * d_block_seg[b] receives the number of segments block b was executed in, for the blocks in front of a run's first failing
+ * one; 0 for every other block and wherever the serial code decoded: the table refused, the scratch refused, or a run of
+ * one block that is no longer than a segment.
+ * gpumt_set_variant(h, "lz4_seg_bytes", n) sets seg_bytes: a power of two, 256 .. 4 MiB, 65536 by default; anything else
+ * is refused with -1 and changes nothing.  GPUMT_LZ4_BLOCK_SEG=0 in the environment or
+ * gpumt_set_variant(h, "lz4_block_seg", 0) make the call gpumt_lz4_decompress_blocks (1 turns it on again; other values are
+ * refused).  Internal scratch: GPUMT_LZ4_SEG_SCRATCH(out_bytes, nblk, seg_bytes) -- the origin plane, which is the cached
+ * allocation of gpumt_lz4_decompress_blocks_par, 12 bytes per possible cut (out_bytes / seg_bytes + nblk: the cut and its
+ * segment's word) and 32 bytes per block; when the device cannot provide it the call decodes serially rather than fail,
+ * keeps the scratch it has, does not ask for that size again, and d_block_seg is 0.
+ */
+#define GPUMT_LZ4_SEG_SCRATCH(out_bytes, nblk, seg_bytes) \
+	(GPUMT_LZ4_PAR_SCRATCH(out_bytes) + 12 * ((size_t)(out_bytes) / (size_t)(seg_bytes) + (size_t)(nblk)) + 32 * (size_t)(nblk) + 256)
+int gpumt_lz4_decompress_blocks_seg(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				    const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
+				    void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
+				    uint32_t *d_status, uint32_t *d_block_seg, int stream);
 /* Ordered concatenation of what the runs decoded: d_pack_off[0..nrun] = exclusive scan of d_run_len and run r's bytes
  * moved from d_out + out_off to d_packed + d_pack_off[r] (d_packed_bytes: its size; must not overlap d_out). */
 int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
@@ -504,8 +533,9 @@ int gpumt_xxh32_batch(gpumt_ctx *h, const void *d_base, const uint64_t *d_off,
  * (gpumt_set_variant("lz4_dec", 2)). */
 int gpumt_debug_counters(gpumt_ctx *h, unsigned long long *dst, int n);
 
-/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre", "zstd_run_par" and "lz4_run_par": 1 = default, 0 = off,
- * anything else is refused with -1 and changes nothing). Returns previous value. */
+/* Kernel-variant selector for A/B measurements (0 = default; "zstd_run_pre", "zstd_run_par", "lz4_run_par" and "lz4_block_seg":
+ * 1 = default, 0 = off, anything else is refused with -1 and changes nothing; "lz4_seg_bytes": see
+ * gpumt_lz4_decompress_blocks_seg). Returns previous value. */
 int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant);
 
 #ifdef __cplusplus

@@ -5,8 +5,9 @@ another on the same streams: the table of profiles/plain_lz4_blocks.txt.
   python tools/plain_lz4_bench.py --mib 1024 --runs 3 --old path/to/parent/libzstdmt_amd.so [--new path] [--out file]
 
 Every run is a process of its own (a library reads its batch size once; a fault ends one run, not the job) under a time
-limit; the two libraries alternate (both see the caller's environment, GPUMT_LZ4_RUN_PAR included).  The callbacks copy 4 MiB per call, so the interpreter's share is a few hundred
-calls per GiB.  GPUMT_TRACE=1 is set for the new library: its per-stage times go into the output."""
+limit; the two libraries alternate (both see the caller's environment, GPUMT_LZ4_RUN_PAR and GPUMT_LZ4_BLOCK_SEG included: a
+library that does not know a variable ignores it).  --legs name,name runs only those streams.  The callbacks copy 4 MiB per
+call, so the interpreter's share is a few hundred calls per GiB.  GPUMT_TRACE=1 is set for the new library: its per-stage times go into the output."""
 import argparse
 import ctypes as C
 import os
@@ -76,6 +77,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--limit", type=int, default=240, help="seconds per run")
     ap.add_argument("--tmp", default="/tmp")
+    ap.add_argument("--legs", default=None, help="comma-separated stream names (default: all)")
     ap.add_argument("--child", nargs=3)
     a = ap.parse_args()
     if a.child:
@@ -90,7 +92,11 @@ def main():
     data = cases.text(n)
     say("# LZ4MT_decompressDCtx, plain .lz4, one frame of %d MiB of the bench text, memcpy callbacks (4 MiB requests)" % a.mib)
     say("# old = %s\n# new = %s\n# %d runs each, alternating old / new; GB/s of content" % (a.old, a.new, a.runs))
+    legs = a.legs.split(",") if a.legs else [name for name, _ in STREAMS]
+    assert all(leg in dict(STREAMS) for leg in legs), legs
     for name, kw in STREAMS:
+        if name not in legs:
+            continue
         path = os.path.join(a.tmp, "plain_%s.lz4" % name)
         with open(path, "wb") as f:
             fr = H.liblz4_frame(data, content_size=0, **kw)

@@ -71,6 +71,18 @@ __global__ void zmt_lz4_par_scan_kernel(const u8 *, u64, const gpumt_lz4_block *
 					u32 *, u32 *, u32 *, Lz4Par);
 __global__ void zmt_lz4_par_exec_kernel(const u8 *, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u8 *, Lz4Par);
 __global__ void zmt_lz4_par_resolve_kernel(const gpumt_lz4_run *, u32, u32, u8 *, u64, u32 *, u32 *, u32 *, Lz4Par);
+/* scratch of gpumt_lz4_decompress_blocks_seg (lz4_dec_seg.h) */
+struct Lz4Seg {
+	u16 *origin;
+	u32 *owner, *mlen, *mst, *pos, *nseg, *cbase, *cut, *xst, *flag;
+	u32 shift, ncut;
+};
+__global__ void zmt_lz4_seg_plan_kernel(const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u64, Lz4Seg);
+__global__ void zmt_lz4_seg_measure_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, Lz4Seg);
+__global__ void zmt_lz4_seg_scan_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u8 *, u64,
+					u32 *, u32 *, u32 *, Lz4Seg);
+__global__ void zmt_lz4_seg_exec_kernel(const u8 *, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u8 *, Lz4Seg);
+__global__ void zmt_lz4_seg_resolve_kernel(const gpumt_lz4_run *, u32, u32, u8 *, u64, u32 *, u32 *, u32 *, u32 *, Lz4Seg);
 __global__ void zmt_lz4_dec_blocks_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u8 *,
 					  u64, u32 *, u32 *, u32 *);
 __global__ void zmt_lz4_gather_runs_kernel(const u8 *, u64, const gpumt_lz4_run *, const u32 *, const u64 *, u32, u8 *,
@@ -171,6 +183,9 @@ struct gpumt_ctx {
 	size_t zrun_par_refused; /* the same for that stage's scratch */
 	int lrun_par;     /* 1 = linked runs of plain .lz4 blocks side by side (gpumt_lz4_decompress_blocks_par); 0 = one wave per run */
 	size_t lrun_par_refused; /* the smallest origin-plane scratch the device has refused (0 = none yet): not asked for again */
+	int lblk_seg;     /* 1 = plain .lz4 blocks in segments side by side (gpumt_lz4_decompress_blocks_seg); 0 = one wave per run */
+	int lseg_bytes;   /* the segment of that call: a power of two, 256 .. 4 MiB */
+	size_t lblk_seg_refused; /* the same for that call's scratch */
 	int sdec_variant; /* snappy decoder: 0 = element by element, 1 = 64 elements per batch (snappy.hip) */
 	int bdec_variant; /* brotli decoder: 0 = by batch size, 1 = the general kernel only, 2 = dec4 (four records per wave) + general for what it hands over */
 	int bdec_waves;   /* resident waves of the persistent brotli decoder kernel (whole device) */
@@ -349,6 +364,16 @@ int gpumt_open(int device, gpumt_ctx **out)
 				h->lrun_par = e[0] - '0';
 			else
 				fprintf(stderr, "gpumt: GPUMT_LZ4_RUN_PAR=%s ignored (0 or 1)\n", e);
+		}
+		/* GPUMT_LZ4_BLOCK_SEG=0: gpumt_lz4_decompress_blocks_seg decodes every run with one wave */
+		e = getenv("GPUMT_LZ4_BLOCK_SEG");
+		h->lblk_seg = 1;
+		h->lseg_bytes = 65536;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				h->lblk_seg = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_LZ4_BLOCK_SEG=%s ignored (0 or 1)\n", e);
 		}
 		/* GPUMT_BROTLI_DEC: 0 = the batch size chooses (default), 1 = the general kernel, 2 = dec4 first */
 		e = getenv("GPUMT_BROTLI_DEC");
@@ -1146,6 +1171,78 @@ int gpumt_lz4_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t s
 	return GPUMT_OK;
 }
 
+int gpumt_lz4_decompress_blocks_seg(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				    const gpumt_lz4_block *d_blocks, size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun,
+				    void *d_out, size_t out_bytes, uint32_t *d_block_len, uint32_t *d_run_len,
+				    uint32_t *d_status, uint32_t *d_block_seg, int s)
+{
+	if (!h || !STREAM_OK(s) || !d_stream || !d_blocks || !d_runs || !d_out || !d_block_len || !d_run_len || !d_status ||
+	    !d_block_seg || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	/* the origin plane, then the cuts (two words each), one word per slot, six words per block + the plan's flag */
+	const size_t seg = (size_t)h->lseg_bytes, ncut = out_bytes / seg + nblk;
+	const size_t plane = (GPUMT_LZ4_PAR_SCRATCH(out_bytes) + 255) & ~(size_t)255;
+	const size_t need = (GPUMT_LZ4_SEG_SCRATCH(out_bytes, nblk, seg) + 512 + 0xFFFFF) & ~(size_t)0xFFFFF;
+	int par = h->lblk_seg != 0 && nblk != 0 && ncut + nblk <= 0x7FFFFFFFu &&
+		  !(h->lblk_seg_refused && need >= h->lblk_seg_refused);
+	if (nblk)
+		CK(hipMemsetAsync(d_block_seg, 0, nblk * 4, h->st[s]));
+	if (par && need > h->scratch_bytes[1][s]) {
+		/* as gpumt_lz4_decompress_blocks_par, whose cached area this is */
+		void *p = dev_alloc(h, need);
+		if (!p) {
+			(void)hipGetLastError(); /* (a refused allocation is no error of this call) */
+			h->lblk_seg_refused = need;
+			par = 0;
+		} else {
+			if (h->scratch[1][s]) {
+				if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+					dev_free(h, p);
+					return GPUMT_E_HIP;
+				}
+				dev_free(h, h->scratch[1][s]);
+			}
+			h->scratch[1][s] = p;
+			h->scratch_bytes[1][s] = need;
+		}
+	}
+	if (!par)
+		return gpumt_lz4_decompress_blocks(h, d_stream, stream_bytes, d_blocks, nblk, d_runs, nrun, d_out, out_bytes,
+						   d_block_len, d_run_len, d_status, s);
+	Lz4Seg P;
+	P.origin = (u16 *)h->scratch[1][s];
+	P.cut = (u32 *)((u8 *)h->scratch[1][s] + plane);
+	P.xst = P.cut + 2 * ncut;
+	P.owner = P.xst + ncut + nblk;
+	P.mlen = P.owner + nblk;
+	P.mst = P.mlen + nblk;
+	P.pos = P.mst + nblk;
+	P.nseg = P.pos + nblk;
+	P.cbase = P.nseg + nblk;
+	P.flag = P.cbase + nblk + 1;
+	P.shift = (u32)__builtin_ctzl(seg);
+	P.ncut = (u32)ncut;
+	PROF0(11);
+	CK(hipMemsetAsync(P.owner, 0xFF, nblk * 4, h->st[s]));
+	CK(hipMemsetAsync(P.flag, 0, 4, h->st[s]));
+	hipLaunchKernelGGL(zmt_lz4_seg_plan_kernel, dim3(1), dim3(64), 0, h->st[s], d_blocks, (u32)nblk, d_runs, (u32)nrun,
+			   (u64)out_bytes, P);
+	hipLaunchKernelGGL(zmt_lz4_seg_measure_kernel, dim3((unsigned)nblk), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, P);
+	hipLaunchKernelGGL(zmt_lz4_seg_scan_kernel, dim3((unsigned)nrun), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   (u64)stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out, (u64)out_bytes, d_block_len,
+			   d_run_len, d_status, P);
+	hipLaunchKernelGGL(zmt_lz4_seg_exec_kernel, dim3((unsigned)(ncut + nblk)), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+			   d_blocks, (u32)nblk, d_runs, (u8 *)d_out, P);
+	hipLaunchKernelGGL(zmt_lz4_seg_resolve_kernel, dim3((unsigned)nrun), dim3(1024), 0, h->st[s], d_runs, (u32)nrun,
+			   (u32)nblk, (u8 *)d_out, (u64)out_bytes, d_block_len, d_run_len, d_status, d_block_seg, P);
+	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
 int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const gpumt_lz4_run *d_runs,
 			const uint32_t *d_run_len, size_t nrun, void *d_packed, size_t packed_bytes,
 			uint64_t *d_pack_off, int s)
@@ -1822,6 +1919,16 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 			return -1;
 		prev = h->lrun_par;
 		h->lrun_par = variant;
+	} else if (!strcmp(what, "lz4_block_seg")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->lblk_seg;
+		h->lblk_seg = variant;
+	} else if (!strcmp(what, "lz4_seg_bytes")) {
+		if (variant < 256 || variant > (4 << 20) || (variant & (variant - 1)))
+			return -1;
+		prev = h->lseg_bytes;
+		h->lseg_bytes = variant;
 	} else if (!strcmp(what, "snappy_dec")) {
 		prev = h->sdec_variant;
 		h->sdec_variant = variant;

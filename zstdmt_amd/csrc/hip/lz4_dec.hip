@@ -338,6 +338,7 @@ zmt_lz4_gather_runs_kernel(const u8 *__restrict__ out_base, u64 out_bytes, const
 }
 
 #include "lz4_dec_par.h"
+#include "lz4_dec_seg.h"
 
 #ifdef ZMT_EMU
 /*
@@ -428,6 +429,72 @@ int gpumt_lz4_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t s
 	}
 	emu_lz4_decompress_blocks_par((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
 				      out_bytes, d_block_len, d_run_len, d_status, par_on);
+	return GPUMT_OK;
+}
+
+/* seg_on = 0, a table without blocks, or seg_bytes no power of two in 256 .. 4 MiB: the serial kernel */
+void emu_lz4_decompress_blocks_seg(const u8 *stream, u64 stream_bytes, const void *blocks, u32 nblk, const void *runs,
+				   u32 nrun, u8 *out, u64 out_bytes, u32 *blk_len, u32 *run_len, u32 *status, u32 *block_seg,
+				   int seg_on, u32 seg_bytes)
+{
+	for (u32 b = 0; b < nblk; b++)
+		block_seg[b] = 0;
+	if (!seg_on || !nblk || seg_bytes < 256 || seg_bytes > (4u << 20) || (seg_bytes & (seg_bytes - 1))) {
+		emu_lz4_decompress_blocks(stream, stream_bytes, blocks, nblk, runs, nrun, out, out_bytes, blk_len, run_len, status);
+		return;
+	}
+	const u32 ncut = (u32)(out_bytes / seg_bytes) + nblk;
+	std::vector<u16> origin((size_t)out_bytes + 4, 0xA5A5); /* scratch starts as garbage */
+	std::vector<u32> owner(nblk, LZ4P_NONE), words((size_t)5 * nblk + 1, 0xA5A5A5A5u), cuts((size_t)2 * ncut, 0xA5A5A5A5u),
+		xst((size_t)ncut + nblk, 0xA5A5A5A5u), flag(1, 0);
+	Lz4Seg P;
+	P.origin = origin.data();
+	P.owner = owner.data();
+	P.mlen = words.data();
+	P.mst = P.mlen + nblk;
+	P.pos = P.mst + nblk;
+	P.nseg = P.pos + nblk;
+	P.cbase = P.nseg + nblk;
+	P.cut = cuts.data();
+	P.xst = xst.data();
+	P.flag = flag.data();
+	P.shift = (u32)__builtin_ctz(seg_bytes);
+	P.ncut = ncut;
+	const Lz4Block *B = (const Lz4Block *)blocks;
+	const Lz4Run *R = (const Lz4Run *)runs;
+	emu::launch(emu::dim3{1, 1, 1}, emu::dim3{64, 1, 1}, [=]() { zmt_lz4_seg_plan_kernel(B, nblk, R, nrun, out_bytes, P); });
+	emu::launch(emu::dim3{nblk, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_lz4_seg_measure_kernel(stream, stream_bytes, B, nblk, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_lz4_seg_scan_kernel(stream, stream_bytes, B, nblk, R, nrun, out, out_bytes, blk_len, run_len, status, P);
+	});
+	emu::launch(emu::dim3{ncut + nblk, 1, 1}, emu::dim3{64, 1, 1}, [=]() { zmt_lz4_seg_exec_kernel(stream, B, nblk, R, out, P); });
+	emu::launch(emu::dim3{nrun, 1, 1}, emu::dim3{LZ4P_RESOLVE_THREADS, 1, 1}, [=]() {
+		zmt_lz4_seg_resolve_kernel(R, nrun, nblk, out, out_bytes, blk_len, run_len, status, block_seg, P);
+	});
+}
+
+int gpumt_lz4_decompress_blocks_seg(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const gpumt_lz4_block *d_blocks,
+				    size_t nblk, const gpumt_lz4_run *d_runs, size_t nrun, void *d_out, size_t out_bytes,
+				    uint32_t *d_block_len, uint32_t *d_run_len, uint32_t *d_status, uint32_t *d_block_seg, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || !d_stream || !d_blocks || !d_runs || !d_out || !d_block_len || !d_run_len ||
+	    !d_status || !d_block_seg || nrun == 0 || nrun > GPUMT_LZ4_BLOCKS_MAX || nblk > GPUMT_LZ4_BLOCKS_MAX)
+		return GPUMT_E_ARG;
+	/* (the emulated boundary keeps no variants: the environment alone, read once and validated as gpumt_open does) */
+	static int seg_on = -1;
+	if (seg_on < 0) {
+		const char *e = getenv("GPUMT_LZ4_BLOCK_SEG");
+		seg_on = 1;
+		if (e && *e) {
+			if ((e[0] == '0' || e[0] == '1') && !e[1])
+				seg_on = e[0] - '0';
+			else
+				fprintf(stderr, "gpumt: GPUMT_LZ4_BLOCK_SEG=%s ignored (0 or 1)\n", e);
+		}
+	}
+	emu_lz4_decompress_blocks_seg((const u8 *)d_stream, stream_bytes, d_blocks, (u32)nblk, d_runs, (u32)nrun, (u8 *)d_out,
+				      out_bytes, d_block_len, d_run_len, d_status, d_block_seg, seg_on, 65536u);
 	return GPUMT_OK;
 }
 

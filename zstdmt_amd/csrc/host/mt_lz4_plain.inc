@@ -6,7 +6,8 @@
  * checksum, end mark, content checksum; skippable frames in between are dropped), every block that is complete in the
  * buffer goes into the batch's block table, and the device decodes the table with gpumt_lz4_decompress_blocks --
  * independent blocks one wave each, the blocks of a linked frame in order by one wave (or, under GPUMT_LZ4_RUN_PAR=1,
- * side by side with gpumt_lz4_decompress_blocks_par), with the last 64 KiB of the frame's earlier output copied in
+ * side by side with gpumt_lz4_decompress_blocks_par; under GPUMT_LZ4_BLOCK_SEG=1 every block in segments side by side
+ * with gpumt_lz4_decompress_blocks_seg), with the last 64 KiB of the frame's earlier output copied in
  * front of the batch's output.  Neither mode needs the whole frame: host memory is
  * about two batches of input plus one block whatever the frame size, and there is no limit on a frame's size.
  * The content checksum is one serial XXH32 chain over the frame; its state lives on the device, is continued batch by
@@ -24,6 +25,7 @@
  * compression_library -- an error, not another way to decode. */
 extern __typeof__(gpumt_lz4_decompress_blocks) gpumt_lz4_decompress_blocks __attribute__((weak));
 extern __typeof__(gpumt_lz4_decompress_blocks_par) gpumt_lz4_decompress_blocks_par __attribute__((weak));
+extern __typeof__(gpumt_lz4_decompress_blocks_seg) gpumt_lz4_decompress_blocks_seg __attribute__((weak));
 extern __typeof__(gpumt_lz4_pack_runs) gpumt_lz4_pack_runs __attribute__((weak));
 extern __typeof__(gpumt_xxh32_carry) gpumt_xxh32_carry __attribute__((weak));
 extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
@@ -43,7 +45,8 @@ extern __typeof__(gpumt_memcpy_d2d) gpumt_memcpy_d2d __attribute__((weak));
 #define PL_OFF_DIGEST (PL_OFF_STATUS + 4 * PL_MAXB)
 #define PL_OFF_VERDICT (PL_OFF_DIGEST + 4 * PL_MAXB)
 #define PL_OFF_PACKOFF (PL_OFF_VERDICT + 4 * PL_MAXB)
-#define PL_META_BYTES (PL_OFF_PACKOFF + 8 * (PL_MAXB + 1) + 64)
+#define PL_OFF_BLKSEG (PL_OFF_PACKOFF + 8 * (PL_MAXB + 1))
+#define PL_META_BYTES (PL_OFF_BLKSEG + 4 * PL_MAXB + 64)
 #define PL_AT(type, meta, dev, off) ((type *)((uint8_t *)((dev) ? (meta)->d : (meta)->h) + (off)))
 
 struct pl_frame { /* the frame the walker is inside of */
@@ -124,7 +127,7 @@ static size_t lz4_plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_
 	const uint8_t *hist_src = NULL; /* device: the end of the open linked frame's output so far */
 	dbuf pack = {0, 0, 0};
 	double t_read = 0, t_dec = 0, t_pack = 0, t_back = 0, t_write = 0, t_chk = 0, t0;
-	size_t nbatch = 0, npack = 0, nblocks = 0;
+	size_t nbatch = 0, npack = 0, nblocks = 0, seg_blocks = 0, seg_segs = 0, seg_serial = 0;
 
 	/* GPUMT_LZ4_RUN_PAR: 1 = the blocks of a linked run side by side (gpumt_lz4_decompress_blocks_par), 0 = one wave per
 	 * run; unset or any other value: PL_PAR_DEFAULT, as profiles/plain_lz4_blocks.txt decided it.  The call keeps an origin
@@ -135,6 +138,10 @@ static size_t lz4_plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_
 	__typeof__(gpumt_lz4_decompress_blocks) *const decode_blocks =
 		gpumt_lz4_decompress_blocks_par && (par_set ? par_env[0] == '1' : PL_PAR_DEFAULT) ? gpumt_lz4_decompress_blocks_par
 												      : gpumt_lz4_decompress_blocks;
+	/* GPUMT_LZ4_BLOCK_SEG=1 (nothing else): every batch with gpumt_lz4_decompress_blocks_seg, big blocks in segments side by
+	 * side, linked runs included, so it wins over GPUMT_LZ4_RUN_PAR; same bytes and verdicts, the same fall-backs */
+	const char *seg_env = getenv("GPUMT_LZ4_BLOCK_SEG");
+	const int seg_on = gpumt_lz4_decompress_blocks_seg && seg_env && seg_env[0] == '1' && !seg_env[1];
 
 	memset(&fr, 0, sizeof fr);
 	if (!gpumt_lz4_decompress_blocks || !gpumt_lz4_pack_runs || !gpumt_xxh32_carry || !gpumt_memcpy_d2d) {
@@ -393,10 +400,21 @@ static size_t lz4_plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_
 					}
 					rc |= gpumt_memcpy_d2d(g, s->out.d, hist_src - hist, hist, 0);
 				}
-				rc |= decode_blocks(g, s->in.d, in_bytes, PL_AT(gpumt_lz4_block, &s->meta, 1, PL_OFF_BLOCKS), nblk,
-						    PL_AT(gpumt_lz4_run, &s->meta, 1, PL_OFF_RUNS), nrun, s->out.d, out_bytes,
-						    PL_AT(uint32_t, &s->meta, 1, PL_OFF_BLKLEN), PL_AT(uint32_t, &s->meta, 1, PL_OFF_RUNLEN),
-						    PL_AT(uint32_t, &s->meta, 1, PL_OFF_STATUS), 0);
+				if (seg_on) {
+					rc |= gpumt_lz4_decompress_blocks_seg(
+						g, s->in.d, in_bytes, PL_AT(gpumt_lz4_block, &s->meta, 1, PL_OFF_BLOCKS), nblk,
+						PL_AT(gpumt_lz4_run, &s->meta, 1, PL_OFF_RUNS), nrun, s->out.d, out_bytes,
+						PL_AT(uint32_t, &s->meta, 1, PL_OFF_BLKLEN), PL_AT(uint32_t, &s->meta, 1, PL_OFF_RUNLEN),
+						PL_AT(uint32_t, &s->meta, 1, PL_OFF_STATUS), PL_AT(uint32_t, &s->meta, 1, PL_OFF_BLKSEG), 0);
+					if (ctx->gpus.trace)
+						rc |= gpumt_memcpy_d2h(g, PL_AT(void, &s->meta, 0, PL_OFF_BLKSEG),
+								       PL_AT(void, &s->meta, 1, PL_OFF_BLKSEG), nblk * 4, 0);
+				} else {
+					rc |= decode_blocks(g, s->in.d, in_bytes, PL_AT(gpumt_lz4_block, &s->meta, 1, PL_OFF_BLOCKS), nblk,
+							    PL_AT(gpumt_lz4_run, &s->meta, 1, PL_OFF_RUNS), nrun, s->out.d, out_bytes,
+							    PL_AT(uint32_t, &s->meta, 1, PL_OFF_BLKLEN), PL_AT(uint32_t, &s->meta, 1, PL_OFF_RUNLEN),
+							    PL_AT(uint32_t, &s->meta, 1, PL_OFF_STATUS), 0);
+				}
 				rc |= gpumt_memcpy_d2h(g, run_len, PL_AT(void, &s->meta, 1, PL_OFF_RUNLEN), nrun * 4, 0);
 				rc |= gpumt_memcpy_d2h(g, status, PL_AT(void, &s->meta, 1, PL_OFF_STATUS), nrun * 4, 0);
 				rc |= gpumt_stream_sync(g, 0);
@@ -404,6 +422,14 @@ static size_t lz4_plain_decompress(MTP(DCtx) *ctx, MTP(RdWr_t) *io, const uint8_
 				if (rc) {
 					err = MTP(ERROR)(compression_library);
 					break;
+				}
+				if (seg_on && ctx->gpus.trace) {
+					const uint32_t *bs = PL_AT(uint32_t, &s->meta, 0, PL_OFF_BLKSEG);
+					for (size_t k = 0; k < nblk; k++) {
+						seg_blocks++;
+						seg_segs += bs[k];
+						seg_serial += bs[k] == 0;
+					}
 				}
 				for (size_t r = 0; r < nrun; r++) {
 					if (status[r] != GPUMT_ST_OK) {
@@ -520,6 +546,8 @@ out:
 	if (ctx->gpus.trace)
 		fprintf(stderr, "[lz4mt plain par] linked runs %s\n",
 			decode_blocks != gpumt_lz4_decompress_blocks ? "block-parallel" : "one wave each");
+	if (ctx->gpus.trace && seg_on)
+		fprintf(stderr, "[lz4mt plain seg] %zu blocks in %zu segments, %zu serial\n", seg_blocks, seg_segs, seg_serial);
 	dbuf_free(g, &pack);
 	if (d_states)
 		gpumt_free(g, d_states);

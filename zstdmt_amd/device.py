@@ -209,9 +209,12 @@ class Engine:
         d_bl = self.upload(np.full(nblk + 1, blk_fill, np.uint32))
         d_rl, d_st = self.alloc(nrun * 4), self.alloc(nrun * 4)
         d_pk, d_po = self.alloc(int(out_bytes) + 64), self.alloc((nrun + 1) * 8)
+        seg = call == "gpumt_lz4_decompress_blocks_seg"
+        d_bs = self.upload(np.full(nblk + 1, 0xA5A5A5A5, np.uint32)) if seg else None
         try:
             self._ck(getattr(self.L, call)(self.h, d_stream.ptr, len(stream), d_blk.ptr, nblk, d_run.ptr, nrun,
-                                           d_out.ptr, int(out_bytes), d_bl.ptr, d_rl.ptr, d_st.ptr, 0), call[6:])
+                                           d_out.ptr, int(out_bytes), d_bl.ptr, d_rl.ptr, d_st.ptr,
+                                           *((d_bs.ptr, 0) if seg else (0,))), call[6:])
             status = self.download(d_st, nrun * 4, np.uint32)
             run_len = self.download(d_rl, nrun * 4, np.uint32)
             blk_len = self.download(d_bl, nblk * 4, np.uint32)
@@ -223,8 +226,12 @@ class Engine:
                                                     int(out_bytes), d_po.ptr, 0), "lz4_pack_runs")
                 total = int(self.download(d_po, (nrun + 1) * 8, np.uint64)[nrun])
                 out = self.download(d_pk, total).tobytes()
+            if seg:
+                blk_seg = self.download(d_bs, (nblk + 1) * 4, np.uint32)
+                assert int(blk_seg[nblk]) == 0xA5A5A5A5, "decoder wrote past the end of block_seg"
+                return out, blk_len, run_len, status, blk_seg[:nblk]
         finally:
-            for b in (d_stream, d_blk, d_run, d_out, d_bl, d_rl, d_st, d_pk, d_po):
+            for b in (d_stream, d_blk, d_run, d_out, d_bl, d_rl, d_st, d_pk, d_po) + ((d_bs,) if seg else ()):
                 b.free()
         return out, blk_len, run_len, status
 
@@ -233,6 +240,12 @@ class Engine:
         arguments and results of lz4_decompress_blocks"""
         return self.lz4_decompress_blocks(stream, blocks, runs, out_bytes, history, pack, blk_fill,
                                           call="gpumt_lz4_decompress_blocks_par")
+
+    def lz4_decompress_blocks_seg(self, stream: bytes, blocks, runs, out_bytes, history=b"", pack=False, blk_fill=0):
+        """gpumt_lz4_decompress_blocks_seg, the same call with every block decoded in segments side by side: the arguments
+        of lz4_decompress_blocks -> (out, blk_len, run_len, status, block_seg[nblk])"""
+        return self.lz4_decompress_blocks(stream, blocks, runs, out_bytes, history, pack, blk_fill,
+                                          call="gpumt_lz4_decompress_blocks_seg")
 
     def xxh32_carry(self, data: bytes, pieces):
         """XXH32 of `data` continued over `pieces` (lengths that add up to len(data)), one gpumt_xxh32_carry call per piece
