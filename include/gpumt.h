@@ -348,6 +348,32 @@ int gpumt_zstd_compress_batch(gpumt_ctx *h, const void *d_in, size_t n, size_t c
 int gpumt_zstd_level_tier(int level);
 int gpumt_zstd_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
 				    size_t slot_stride, uint32_t *d_rec_len, int level, int stream);
+/*
+ * The same with the whole chunk as the match window (opt-in; what GPUMT_ZSTD_WIN=1 makes ZSTDCB_compressCCtx call at
+ * levels 10-22).  Arguments, slot layout and records are those of gpumt_zstd_compress_batch_level, and levels below 10
+ * are passed straight to it.  From level 10 on a first launch writes a chain plane -- per input byte the nearest earlier
+ * position of the same chunk whose next 6 bytes hash alike -- and the block encoder walks it for up to
+ * gpumt_zstd_win_depth(level) candidates per position (8 for levels 10-12, 16 for 13-15, 32 for 16-18, 64 for 19-22, 0
+ * below 10; levels of one group give the same bytes) and keeps the best by 4 * length - log2(offset + 1), ties to the
+ * nearer.  A match takes its source from any earlier byte of its chunk at a distance of at most 2^27, never from
+ * another chunk, and ends with its 128 KiB block; the frames stay single-segment with a content size, so every offset
+ * is legal.  The bytes depend on the input, the chunk and the level group alone: not on the grid nor on the other
+ * records of the batch.
+ * Internal scratch: GPUMT_ZSTD_WIN_SCRATCH(n) -- 4 bytes per input byte for the plane -- plus 512 KiB of head table per
+ * resident wave of the first launch and the per-wave areas of gpumt_zstd_compress_batch_level.  A batch above 1 GiB is
+ * processed in slices of whole records of at most 1 GiB of input each, so the plane never exceeds 4 GiB.  If the device
+ * refuses the scratch the call encodes with gpumt_zstd_compress_batch_level, remembers the refused size (it is not
+ * asked for again) and, like every call from level 10 on, says so in its GPUMT_TRACE=1 line: records, depth (0 = the
+ * table encoder ran), plane bytes, fallback.  Chunks above 128 MiB, whose frames carry a 128 KiB Window_Descriptor,
+ * take that path as well.
+ * gpumt_set_variant(h, "zstd_win_depth", d) overrides the depth for A/B runs: 1..256, 0 = by level, anything else is
+ * rejected (-1); "zstd_win_cap_mb" (0 = none) refuses scratch requests above that many MiB: the tests' way to the
+ * fallback.
+ */
+#define GPUMT_ZSTD_WIN_SCRATCH(n) ((size_t)4 * (n) + 256)
+int gpumt_zstd_win_depth(int level);
+int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
+				  size_t slot_stride, uint32_t *d_rec_len, int level, int stream);
 
 int gpumt_zstd_probe_sizes(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off,
 			   const uint32_t *d_rec_len, size_t nrec, uint32_t *d_out_len,

@@ -63,6 +63,8 @@ GPUMT_SYMBOLS = {
     "gpumt_zstd_compress_batch": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i]),
     "gpumt_zstd_compress_batch_level": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i, _i]),
     "gpumt_zstd_level_tier": (_i, [_i]),
+    "gpumt_zstd_win_depth": (_i, [_i]),
+    "gpumt_zstd_compress_batch_win": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i, _i]),
     "gpumt_zstd_probe_sizes": (_i, [_vp, _vp, _u64p, _u32p, _sz, _u32p, _u64p, _u32p, _i]),
     "gpumt_zstd_decompress_batch": (_i, [_vp, _vp, _sz, _u64p, _u32p, _sz, _vp, _sz, _u64p, _u32p, _u32p, _i]),
     "gpumt_zstd_decompress_blocks": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _u32p, _u32p, _i]),

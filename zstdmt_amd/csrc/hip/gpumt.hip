@@ -144,6 +144,8 @@ __global__ void zmt_zstd_enc_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u
 __global__ void zmt_zstd_enc_t2_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *);
 __global__ void zmt_zstd_enc_t3_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *);
 __global__ void zmt_zstd_enc_kernel_prof(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *, unsigned long long *);
+__global__ void zmt_zstd_win_chain_kernel(const u8 *, u64, u32, u32, u32 *, u32 *);
+__global__ void zmt_zstd_enc_win_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *, const u32 *, u32);
 __global__ void zmt_zstd_assemble_kernel(u64, u32, u32, u32, u8 *, u64, const u32 *, u32 *);
 __global__ void zmt_zstd_probe_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *, u32 *);
 __global__ void zmt_probe_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *);
@@ -174,6 +176,11 @@ struct gpumt_ctx {
 	int profile; /* record events in timer slots 8.. around individual kernels */
 	int num_cus;
 	int zenc_waves[3]; /* resident waves of the persistent zstd encoder kernels (whole device), per level tier */
+	int zwin_waves;   /* ... of the whole-chunk-window encoder (gpumt_zstd_compress_batch_win) */
+	int zwin_depth;   /* its candidates per position: 0 = by level (gpumt_zstd_win_depth), 1..256 = this many (A/B runs) */
+	int zwin_cap_mb;  /* 0 = none; else scratch requests of that call above this many MiB count as refused (the tests' way to the fallback) */
+	size_t zwin_refused; /* the smallest scratch of that call the device has refused (0 = none yet): not asked for again */
+	int trace;        /* GPUMT_TRACE */
 	int hc_waves;     /* developer: grid of the LZ4HC encoder (0 = GPUMT_LZ4HC_WAVES) */
 	int zdec_variant; /* 0 = small-table kernel, then general; 1 = general only */
 	int zseq_variant; /* 0 = sequence pre-pass (zstd_dec_seq.hip) in front of the frame decoder; 1 = none */
@@ -375,6 +382,8 @@ int gpumt_open(int device, gpumt_ctx **out)
 			else
 				fprintf(stderr, "gpumt: GPUMT_LZ4_BLOCK_SEG=%s ignored (0 or 1)\n", e);
 		}
+		e = getenv("GPUMT_TRACE");
+		h->trace = e && *e ? atoi(e) : 0;
 		/* GPUMT_BROTLI_DEC: 0 = the batch size chooses (default), 1 = the general kernel, 2 = dec4 first */
 		e = getenv("GPUMT_BROTLI_DEC");
 		h->bdec_variant = e && *e ? atoi(e) : 0;
@@ -1287,6 +1296,7 @@ int gpumt_xxh32_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const
 #define ZE_BSTRIDE (ZE_BLOCK + 16u)
 #define ZE_HDR 32u
 #define ZE_MAXSEQ (ZE_BLOCK / 4u)
+#define ZE_WSCRATCH_BYTES ((size_t)3 * ZE_MAXSEQ * 4 + 16 * 20544 + ZE_BLOCK + 64) /* per persistent encoder wave (zstd_enc.hip) */
 
 size_t gpumt_zstd_slot_stride(size_t chunk)
 {
@@ -1358,6 +1368,93 @@ int gpumt_zstd_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, si
 	hipLaunchKernelGGL(zmt_zstd_assemble_kernel, dim3((unsigned)nrec), dim3(256), 0, h->st[s], (u64)n,
 			   (u32)chunk, (u32)nrec, bpr, (u8 *)d_slots, (u64)slot_stride, (const u32 *)blk_len,
 			   d_rec_len);
+	PROF1(9);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+/* ---- the whole chunk as the match window (zstd_enc_win.h) ---- */
+#define ZW_HLOG_MAX 17
+#define ZW_MAXDIST (1u << 27)
+#define ZW_SLICE ((size_t)1 << 30) /* input bytes per launch slice: the plane stays within 4 GiB */
+
+int gpumt_zstd_win_depth(int level) { return level < 10 ? 0 : level <= 12 ? 8 : level <= 15 ? 16 : level <= 18 ? 32 : 64; }
+
+int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
+				  size_t slot_stride, uint32_t *d_rec_len, int level, int s)
+{
+	if (!h || !STREAM_OK(s) || chunk == 0 || chunk > 0x40000000u || slot_stride < gpumt_zstd_slot_stride(chunk) ||
+	    level < 1 || level > 22)
+		return GPUMT_E_ARG;
+	if (level < 10)
+		return gpumt_zstd_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, s);
+	if (use(h))
+		return GPUMT_E_HIP;
+	const size_t nrec = gpumt_lz4_record_count(n, chunk);
+	const u32 bpr = (u32)((chunk + ZE_BLOCK - 1) / ZE_BLOCK);
+	if (nrec * bpr > 0x7FFFFFFFu)
+		return GPUMT_E_ARG;
+	const u32 depth = h->zwin_depth ? (u32)h->zwin_depth : (u32)gpumt_zstd_win_depth(level);
+	if (!h->zwin_waves) {
+		int per_cu = 0;
+		CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, zmt_zstd_enc_win_kernel, 64, 0));
+		h->zwin_waves = (per_cu > 0 ? per_cu : 4) * (h->num_cus > 0 ? h->num_cus : 256);
+	}
+	/* slices of whole records, at most ZW_SLICE input bytes each; every slice sizes the same scratch */
+	const size_t rps = chunk >= ZW_SLICE ? 1 : ZW_SLICE / chunk, slice_rec = nrec < rps ? nrec : rps;
+	const size_t slice_in = slice_rec * chunk < n ? slice_rec * chunk : n, slice_blk = slice_rec * bpr;
+	const size_t egrid = slice_blk < (size_t)h->zwin_waves ? slice_blk : (size_t)h->zwin_waves;
+	const size_t cwaves = (size_t)4 * (h->num_cus > 0 ? h->num_cus : 256), cgrid = slice_rec < cwaves ? slice_rec : cwaves;
+	const size_t o_seq = (slice_blk * 4 + 255) & ~(size_t)255, o_head = o_seq + ((egrid * ZE_WSCRATCH_BYTES + 255) & ~(size_t)255);
+	const size_t o_plane = o_head + (cgrid * 4 << ZW_HLOG_MAX);
+	const size_t need = (o_plane + GPUMT_ZSTD_WIN_SCRATCH(slice_in) + 0xFFFFF) & ~(size_t)0xFFFFF;
+	/* chunks above 128 MiB carry a 128 KiB Window_Descriptor (zmt_zstd_assemble_kernel): the table encoder's */
+	int win = chunk <= ZW_MAXDIST && !(h->zwin_refused && need >= h->zwin_refused);
+	if (win && h->zwin_cap_mb && need > ((size_t)h->zwin_cap_mb << 20)) {
+		h->zwin_refused = need;
+		win = 0;
+	}
+	if (win && need > h->scratch_bytes[0][s]) {
+		/* ask before letting go of the area the stream has: a refusal must leave the table encoder its scratch */
+		void *p = dev_alloc(h, need);
+		if (!p) {
+			(void)hipGetLastError(); /* (a refused allocation is no error of this call) */
+			h->zwin_refused = need;
+			win = 0;
+		} else {
+			if (h->scratch[0][s]) {
+				if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+					dev_free(h, p);
+					return GPUMT_E_HIP;
+				}
+				dev_free(h, h->scratch[0][s]);
+			}
+			h->scratch[0][s] = p;
+			h->scratch_bytes[0][s] = need;
+		}
+	}
+	if (h->trace >= 1)
+		fprintf(stderr, "[gpumt zstd win] records %zu depth %u plane %zu fallback %d\n", nrec, win ? depth : 0u,
+			win ? (size_t)4 * slice_in : (size_t)0, win ? 0 : 1);
+	if (!win)
+		return gpumt_zstd_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, s);
+	u32 *blk_len = (u32 *)h->scratch[0][s];
+	u8 *seqbuf = (u8 *)h->scratch[0][s] + o_seq;
+	u32 *heads = (u32 *)((u8 *)h->scratch[0][s] + o_head), *plane = (u32 *)((u8 *)h->scratch[0][s] + o_plane);
+	PROF0(9);
+	for (size_t r0 = 0; r0 < nrec; r0 += slice_rec) {
+		const size_t nr = nrec - r0 < slice_rec ? nrec - r0 : slice_rec, i0 = r0 * chunk;
+		const size_t ni = n - i0 < nr * chunk ? n - i0 : nr * chunk, nb = nr * bpr;
+		const unsigned eg = (unsigned)(nb < egrid ? nb : egrid), cg = (unsigned)(nr < cgrid ? nr : cgrid);
+		const u8 *in = (const u8 *)d_in + i0;
+		u8 *slots = (u8 *)d_slots + r0 * slot_stride;
+		hipLaunchKernelGGL(zmt_zstd_win_chain_kernel, dim3(cg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nr, plane,
+				   heads);
+		hipLaunchKernelGGL(zmt_zstd_enc_win_kernel, dim3(eg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nb, bpr, slots,
+				   (u64)slot_stride, blk_len, seqbuf, (const u32 *)plane, depth);
+		hipLaunchKernelGGL(zmt_zstd_assemble_kernel, dim3((unsigned)nr), dim3(256), 0, h->st[s], (u64)ni, (u32)chunk, (u32)nr,
+				   bpr, slots, (u64)slot_stride, (const u32 *)blk_len, d_rec_len + r0);
+	}
 	PROF1(9);
 	CK(hipGetLastError());
 	return GPUMT_OK;
@@ -1914,6 +2011,17 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 			return -1;
 		prev = h->zrun_par;
 		h->zrun_par = variant;
+	} else if (!strcmp(what, "zstd_win_depth")) {
+		if (variant < 0 || variant > 256)
+			return -1;
+		prev = h->zwin_depth;
+		h->zwin_depth = variant;
+	} else if (!strcmp(what, "zstd_win_cap_mb")) {
+		if (variant < 0)
+			return -1;
+		prev = h->zwin_cap_mb;
+		h->zwin_cap_mb = variant;
+		h->zwin_refused = 0; /* (a new cap: ask again) */
 	} else if (!strcmp(what, "lz4_run_par")) {
 		if (variant != 0 && variant != 1)
 			return -1;

@@ -875,12 +875,17 @@ static __device__ u32 ze_huf_encode(ZEncLds &L, u32 *stage, const ZHuf hf, const
 		}                                                                                  \
 	} while (0)
 
-template <bool PROF, int HB, u32 MM, int HLOG, bool REP = (ZE_REP != 0), u32 LAZYW = ZE_LAZYW>
+#include "zstd_enc_win.h"
+
+/* WIN: the match finder is ze_win_find over the chunk's chain plane (zstd_enc_win.h) instead of the LDS table; a candidate
+ * may then lie in an earlier block of the chunk (a block-relative position below 0, see ze_at) */
+template <bool PROF, int HB, u32 MM, int HLOG, bool REP = (ZE_REP != 0), u32 LAZYW = ZE_LAZYW, bool WIN = false>
 static __device__ __forceinline__ void
 zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_total, u32 blk_per_rec,
 	      u8 *__restrict__ slots, u64 stride, u32 *__restrict__ blk_len, u8 *__restrict__ scratch,
-	      unsigned long long *prof)
+	      unsigned long long *prof, const u32 *__restrict__ plane = nullptr, u32 depth = 0)
 {
+	constexpr u32 NOCAND = WIN ? ZW_FAR : 0xFFFFFFFFu; /* "no candidate" among the block-relative positions */
 	const int lane = wv_lane();
 	u64 pc[PROF ? 8 : 1] = {0}, tq = ZET();
 	const u64 t_begin = tq;
@@ -947,9 +952,11 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 		 * the pointer is derived from the byte address of the enclosing object, never from the 4 Ki-entry member array
 		 * (indexing that array past its end would be undefined) */
 		u16 *const tab = (u16 *)((u8 *)&L + offsetof(ZEncLds, table));
-		for (u32 i = (u32)lane; i < (1u << HLOG); i += 64)
-			tab[i] = 0;
-		wv_sync();
+		if (!WIN) {
+			for (u32 i = (u32)lane; i < (1u << HLOG); i += 64)
+				tab[i] = 0;
+			wv_sync();
+		}
 		u32 ns = 0, anchor = 0, cursor = 0;
 		u32 r_ll = 0, r_ml = 0, r_of = 0;
 		/* rp1: the offset of the newest sequence (0 = none yet in this unit); replive: steps the look-out for repeat matches
@@ -996,6 +1003,13 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 	do {                                                                                       \
 		const u32 p_ = (t) * 64u + (u32)lane;                                              \
 		const bool ok_ = (t) < steps && p_ + MM <= bsize;                                  \
+		if (WIN) {                                                                         \
+			/* the chain walk needs the input's bytes 8..19 for its own compares: asked for here, \
+			 * where the table encoders ask for them behind the lookup */                        \
+			const u8 *iq_ = src + (ok_ ? p_ : 0u);                                     \
+			(Cc) = ze_win_find<MM>(in + cstart, plane + cstart, bstart, bsize, p_, ok_, (V), ld64u(iq_ + 8), \
+					       ld32u(iq_ + 16), depth);                                    \
+		} else {                                                                           \
 		const u32 h_ = ze_hash<HB, HLOG>(V);                                               \
 		const u32 e_ = ok_ ? tab[h_] : 0;                                                  \
 		wv_sync();                                                                         \
@@ -1015,6 +1029,7 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 		/* (the four positions at the very start of a block are no candidates: the window below  \
 		 * starts 4 bytes in front of one) */                                                  \
 		(Cc) = (ok_ && c_ < p_ && c_ >= 4u) ? c_ : 0xFFFFFFFFu;                            \
+		}                                                                                  \
 		/* 24 bytes around the candidate -- 4 in front of it, 20 from it on -- and the same of    \
 		 * the input: most matches are measured right here, without the wave-wide extension     \
 		 * below, and a match grows backwards into the literals in front of it (its first bytes \
@@ -1022,8 +1037,8 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 		 * costs no gather of its own [MI355X, 8 GiB: 92.2 ms without looking back, 108.1 ms    \
 		 * with a separate 4-byte gather, 91.0 ms this way] */                                  \
 		{                                                                                  \
-			const bool v_ = (Cc) != 0xFFFFFFFFu;                                       \
-			const u8 *cp_ = src + (v_ ? (Cc) - 4u : 0u);                               \
+			const bool v_ = (Cc) != NOCAND;                                            \
+			const u8 *cp_ = ze_at<WIN>(src, v_ ? (Cc) - 4u : 0u);                      \
 			const u8 *ip_ = src + ((REP ? ok_ : v_) ? p_ : 0u);                        \
 			(M).v = (V);                                                               \
 			(M).a = ld64u(cp_);                                                        \
@@ -1074,7 +1089,8 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 				RR[(k + 1) % 3] = 0;
 				if (replive) {
 					const u32 pn = (t + 1) * 64u + (u32)lane, rn = rp1;
-					const u8 *rq = src + ((rn && pn >= rn && pn + MM <= bsize) ? pn - rn : 0u);
+					/* (WIN: the offset may reach into the chunk's earlier blocks) */
+					const u8 *rq = ze_at<WIN>(src, (rn && (WIN ? bstart : 0u) + pn >= rn && pn + MM <= bsize) ? pn - rn : 0u);
 					RR[(k + 1) % 3] = rn;
 					RA[(k + 1) % 3] = ld64u(rq);
 					RB[(k + 1) % 3] = ld64u(rq + 8);
@@ -1107,7 +1123,7 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 					m = (z0 < z12 ? z0 : z12) >> 3; /* 8 + 8 + 4 equal bytes: 160 >> 3 = ZE_FWD */
 				}
 #endif
-				const bool cand = c0 != 0xFFFFFFFFu && p >= cursor;
+				const bool cand = c0 != NOCAND && p >= cursor;
 				if (cand && m > bsize - p)
 					m = bsize - p;
 				const u32 xb = m0.pb ^ (u32)m0.a;
@@ -1123,7 +1139,7 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 				 * a step without a look-out pays nothing for it.  (An offset that is no longer the newest would cost as
 				 * much as a new one: not looked at) */
 				if (REP && repR && repR == rp1) {
-					const bool rv = p >= repR && p + MM <= bsize && p >= cursor;
+					const bool rv = (WIN ? bstart : 0u) + p >= repR && p + MM <= bsize && p >= cursor;
 					const u64 y0 = v0 ^ RA[k], y1 = m0.d ^ RB[k];
 					u32 mr = y0 ? (u32)__builtin_ctzll(y0) >> 3 : y1 ? 8u + ((u32)__builtin_ctzll(y1) >> 3) : 16u;
 					const bool full = mr == 16u;
@@ -1138,7 +1154,7 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 #else
 				/* (ballots of one compare each, combined as scalar masks: a ballot of `a && b` compiles to mask algebra plus a
 				 * select and a second compare that re-materialise the mask) */
-				u64 mask = wv_ballot(m >= MM) & wv_ballot(c0 != 0xFFFFFFFFu) & wv_ballot(p >= cursor);
+				u64 mask = wv_ballot(m >= MM) & wv_ballot(c0 != NOCAND) & wv_ballot(p >= cursor);
 				if (REP)
 					mask |= wv_ballot(ur);
 #endif
@@ -1199,7 +1215,7 @@ zstd_enc_body(ZEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_
 							u32 k = 0;
 							bool stop = true;
 							if (pj + o < bsize) {
-								const u64 y = ld64u(src + pj + o) ^ ld64u(src + cj + o);
+								const u64 y = ld64u(src + pj + o) ^ ld64u(ze_at<WIN>(src, cj) + o);
 								k = y ? (u32)__builtin_ctzll(y) >> 3 : 8u;
 								stop = k < 8;
 							}
@@ -1613,6 +1629,18 @@ zmt_zstd_enc_t3_kernel(const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_tot
 	zstd_enc_body<false, 6, 6u, 14>(S.L, in, n, chunk, nblk_total, blk_per_rec, slots, stride, blk_len, scratch, nullptr);
 }
 
+/* the whole-chunk window (levels 10..22, opt-in): candidates from the chain plane of zmt_zstd_win_chain_kernel, `depth` per
+ * position; no hash table in LDS, the entropy-phase arrays alone (the 4 Ki-entry struct) */
+extern "C" __global__ void __launch_bounds__(64)
+zmt_zstd_enc_win_kernel(const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_total, u32 blk_per_rec,
+			u8 *__restrict__ slots, u64 stride, u32 *__restrict__ blk_len, u8 *__restrict__ scratch,
+			const u32 *__restrict__ plane, u32 depth)
+{
+	__shared__ __attribute__((aligned(16))) ZEncLds L;
+	zstd_enc_body<false, 6, 6u, ZE_HLOG, (ZE_REP != 0), ZE_LAZYW, true>(L, in, n, chunk, nblk_total, blk_per_rec, slots, stride,
+									     blk_len, scratch, nullptr, plane, depth);
+}
+
 #ifndef ZMT_EMU
 /* same kernel with per-phase cycle counters (developer tool) */
 extern "C" __global__ void __launch_bounds__(64)
@@ -1708,3 +1736,81 @@ zmt_zstd_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__rest
 		rec_len[rec] = at;
 	}
 }
+
+#ifdef ZMT_EMU
+/*
+ * TEST HARNESS ONLY (tests/emu compiles this file as host C++): gpumt_zstd_compress_batch_win over the fiber emulator, with
+ * the shapes of include/gpumt.h, so that the whole-chunk window and the host engine's GPUMT_ZSTD_WIN path run on the CPU.
+ * Synchronous, host pointers stand in for device pointers; the same argument checks as gpumt.hip.  Never part of the product.
+ */
+#include <vector>
+#include "../../../include/gpumt.h"
+extern "C" {
+void emu_zstd_compress_batch_level(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level);
+size_t emu_zstd_slot_stride(size_t chunk);
+
+int gpumt_zstd_win_depth(int level) { return level < 10 ? 0 : level <= 12 ? 8 : level <= 15 ? 16 : level <= 18 ? 32 : 64; }
+
+/* the chain plane alone (what the tests compare with their own model): plane = one word per input byte */
+void emu_zstd_win_chain(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 grid)
+{
+	const u32 nrec = n ? (u32)((n + chunk - 1) / chunk) : 1;
+	if (grid > nrec)
+		grid = nrec;
+	std::vector<u32> heads((size_t)grid << ZW_HLOG_MAX, 0xA5A5A5A5u); /* scratch starts as garbage */
+	u32 *hd = heads.data();
+	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1}, [=]() { zmt_zstd_win_chain_kernel(in, n, chunk, nrec, plane, hd); });
+}
+
+/* depth: 0 = by level.  cap: the scratch the "device" grants, 0 = any -- a request above it is refused and the call
+ * encodes with the table encoder of the level, as below level 10 and for chunks above 128 MiB.  Returns the depth the
+ * window encoder ran with, 0 where the table encoder ran */
+u32 emu_zstd_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level,
+				u32 depth, u64 cap)
+{
+	const u32 nrec = n ? (u32)((n + chunk - 1) / chunk) : 1;
+	const u32 bpr = (chunk + ZE_BLOCK - 1) / ZE_BLOCK;
+	const u32 nblk = nrec * bpr;
+	if (!depth)
+		depth = (u32)gpumt_zstd_win_depth(level);
+	const u64 need = GPUMT_ZSTD_WIN_SCRATCH(n);
+	if (level < 10 || chunk > ZW_MAXDIST || (cap && need > cap)) {
+		emu_zstd_compress_batch_level(in, n, chunk, slots, stride, rec_len, grid, level);
+		return 0;
+	}
+	if (grid > nblk)
+		grid = nblk;
+	std::vector<u32> blk_len(nblk, 0xA5A5A5A5u), plane((size_t)n + 1, 0xA5A5A5A5u);
+	std::vector<u8> seq((size_t)grid * ZE_WSCRATCH, 0xA5);
+	u32 *bl = blk_len.data(), *pl = plane.data();
+	u8 *sq = seq.data();
+	emu_zstd_win_chain(in, n, chunk, pl, grid);
+	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_zstd_enc_win_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq, pl, depth); });
+	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_zstd_assemble_kernel(n, chunk, nrec, bpr, slots, stride, bl, rec_len); });
+	return depth;
+}
+
+/* (the emulated boundary keeps no variants: GPUMT_ZSTD_WIN_DEPTH and GPUMT_ZSTD_WIN_CAP -- bytes -- stand in for
+ * gpumt_set_variant's "zstd_win_depth" and "zstd_win_cap_mb") */
+int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
+				  uint32_t *d_rec_len, int level, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || chunk == 0 || chunk > 0x40000000u || slot_stride < emu_zstd_slot_stride(chunk) ||
+	    level < 1 || level > 22)
+		return GPUMT_E_ARG;
+	const char *e = getenv("GPUMT_ZSTD_WIN_DEPTH"), *c = getenv("GPUMT_ZSTD_WIN_CAP"), *t = getenv("GPUMT_TRACE");
+	const long dv = e && *e ? atol(e) : 0;
+	const u64 cap = c && *c ? strtoull(c, 0, 10) : 0;
+	if (dv < 0 || dv > 256)
+		return GPUMT_E_ARG;
+	const u32 ran = emu_zstd_compress_batch_win((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3, level,
+						    (u32)dv, cap);
+	if (t && atoi(t) >= 1 && level >= 10)
+		fprintf(stderr, "[gpumt zstd win] records %zu depth %u plane %zu fallback %d\n", n ? (n + chunk - 1) / chunk : (size_t)1, ran,
+			ran ? (size_t)4 * n : (size_t)0, ran ? 0 : 1);
+	return GPUMT_OK;
+}
+}
+#endif

@@ -84,8 +84,21 @@ static const int window_log[] = {19, 19, 20, 20, 20, 21, 21, 21, 21, 21, 22, 22,
 #define MT_LEVEL_OK(level) ((level) >= ZSTDCB_LEVEL_MIN && (level) <= ZSTDCB_LEVEL_MAX)
 #define MT_DEFAULT_CHUNK(level) (1 << (window_log[level] + 1))
 #define MT_SLOT_STRIDE(chunk) gpumt_zstd_slot_stride(chunk)
-/* three device tiers for the level: gpumt_zstd_level_tier */
-#define MT_COMPRESS_BATCH gpumt_zstd_compress_batch_level
+/* three device tiers for the level: gpumt_zstd_level_tier.  GPUMT_ZSTD_WIN=1 (exactly that) hands levels 10-22 to the
+ * whole-chunk-window encoder instead, gpumt_zstd_compress_batch_win: same slots, same records, smaller frames; unset or
+ * anything else, and below level 10, the call is the one above, byte for byte.  The variable is read per batch (the
+ * launching thread alone reads it).  A weak reference, as in mt_lz4_plain.inc: a stand-in for the device boundary that
+ * lacks the call leaves the engine on the table encoder */
+extern __typeof__(gpumt_zstd_compress_batch_win) gpumt_zstd_compress_batch_win __attribute__((weak));
+static int zstd_compress_batch(gpumt_ctx *g, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t stride,
+			       uint32_t *d_len, int level, int stream)
+{
+	const char *e = level >= 10 && gpumt_zstd_compress_batch_win ? getenv("GPUMT_ZSTD_WIN") : NULL;
+	if (e && e[0] == '1' && !e[1])
+		return gpumt_zstd_compress_batch_win(g, d_in, n, chunk, d_slots, stride, d_len, level, stream);
+	return gpumt_zstd_compress_batch_level(g, d_in, n, chunk, d_slots, stride, d_len, level, stream);
+}
+#define MT_COMPRESS_BATCH zstd_compress_batch
 #define MT_BATCH_UNIT(chunk) (chunk)
 #define MT_C_DEVICE_ERROR compression_library
 #define MT_C_NULL_CTX init_missing

@@ -386,10 +386,14 @@ class Engine:
     def zstd_slot_stride(self, chunk):
         return int(self.L.gpumt_zstd_slot_stride(chunk))
 
-    def zstd_compress(self, d_in, n, chunk, d_slots, stride, d_rec_len, stream=0, level=1):
-        self._ck(self.L.gpumt_zstd_compress_batch_level(self.h, d_in.ptr, int(n), int(chunk), d_slots.ptr,
-                                                        int(stride), d_rec_len.ptr, int(level), stream),
-                 "zstd_compress_batch_level")
+    def zstd_compress(self, d_in, n, chunk, d_slots, stride, d_rec_len, stream=0, level=1, win=False):
+        """win=True: gpumt_zstd_compress_batch_win, the whole chunk as the match window from level 10 on"""
+        call = self.L.gpumt_zstd_compress_batch_win if win else self.L.gpumt_zstd_compress_batch_level
+        self._ck(call(self.h, d_in.ptr, int(n), int(chunk), d_slots.ptr, int(stride), d_rec_len.ptr, int(level), stream),
+                 "zstd_compress_batch_win" if win else "zstd_compress_batch_level")
+
+    def zstd_win_depth(self, level):
+        return int(self.L.gpumt_zstd_win_depth(int(level)))
 
     def zstd_probe(self, d_stream, d_rec_off, d_rec_len, nrec, d_out_len, d_out_off, d_status, stream=0):
         self._ck(self.L.gpumt_zstd_probe_sizes(self.h, d_stream.ptr, d_rec_off.ptr, d_rec_len.ptr, nrec,
@@ -459,8 +463,9 @@ class Engine:
         return recs, status
 
     # ---- convenience round trips on host bytes (tests) ----------------------------------------
-    def compress_bytes(self, data: bytes, chunk: int, codec="lz4", level=1):
-        """-> (stream bytes, rec_off[n+1] u64, rec_len[n] u32)"""
+    def compress_bytes(self, data: bytes, chunk: int, codec="lz4", level=1, win=False):
+        """-> (stream bytes, rec_off[n+1] u64, rec_len[n] u32); win: codec "zstd" with the whole-chunk window"""
+        assert not win or codec == "zstd"
         n = len(data)
         nrec = self.record_count(n, chunk)
         stride = self.zstd_slot_stride(chunk) if codec in ("zstd", "brotli") else self.slot_stride(chunk)
@@ -470,7 +475,7 @@ class Engine:
         d_off = self.alloc((nrec + 1) * 8)
         try:
             if codec == "zstd":
-                self.zstd_compress(d_in, n, chunk, d_slots, stride, d_len, level=level)
+                self.zstd_compress(d_in, n, chunk, d_slots, stride, d_len, level=level, win=win)
             elif codec == "brotli":
                 self.brotli_compress(d_in, n, chunk, d_slots, stride, d_len, level=level)
             else:
