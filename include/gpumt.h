@@ -517,6 +517,33 @@ int gpumt_brotli_compress_batch(gpumt_ctx *h, const void *d_in, size_t n, size_t
 int gpumt_brotli_level_tier(int level);
 int gpumt_brotli_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
 				      size_t slot_stride, uint32_t *d_rec_len, int level, int stream);
+/*
+ * The same with the whole chunk as the match window (opt-in; what GPUMT_BROTLI_WIN=1 makes BROTLIMT_compressCCtx call at
+ * qualities 9-11).  Arguments, slot layout and records are those of gpumt_brotli_compress_batch_level, and qualities below
+ * 9 are passed straight to it.  From quality 9 on a first launch writes the chain plane of gpumt_zstd_compress_batch_win --
+ * per input byte the nearest earlier position of the same chunk whose next 6 bytes hash alike; the same kernel -- and the
+ * block encoder walks it for up to gpumt_brotli_win_depth(level) candidates per position (16 / 32 / 64 for qualities 9 /
+ * 10 / 11, 0 below 9), measures each on 24 bytes and keeps the best by 4 * length - log2(distance + 1), ties to the nearer.
+ * A match takes its source from any earlier byte of its chunk, never from another chunk, and ends with its 128 KiB
+ * meta-block.  Every stream declares the smallest WBITS in 18..24 whose window, (1 << WBITS) - 16, holds the chunk's largest
+ * distance (else 24), and no distance exceeds min(position in the chunk, that window), so none can be read as a reference
+ * into the static dictionary; chunks above 16 MiB stay on this path and rely on the cap.  NPOSTFIX = NDIRECT = 0, no
+ * context modelling, as before.  The bytes depend on the input, the chunk and the quality alone: not on the grid nor on the
+ * other records of the batch.
+ * Internal scratch: GPUMT_BROTLI_WIN_SCRATCH(n) -- 4 bytes per input byte for the plane -- plus 512 KiB of head table per
+ * resident wave of the first launch and the per-wave areas of gpumt_brotli_compress_batch_level.  A batch above 1 GiB is
+ * processed in slices of whole records of at most 1 GiB of input each.  If the device refuses the scratch the call encodes
+ * with gpumt_brotli_compress_batch_level, remembers the refused size (it is not asked for again) and, like every call from
+ * quality 9 on, says so in its GPUMT_TRACE=1 line: `[gpumt brotli win] records N depth D plane B fallback F` (depth 0 = the
+ * table encoder ran).
+ * gpumt_set_variant(h, "brotli_win_depth", d) overrides the depth for A/B runs: 1..256, 0 = by level, anything else is
+ * rejected (-1); "brotli_win_cap_mb" (0 = none) refuses scratch requests above that many MiB: the tests' way to the
+ * fallback.
+ */
+#define GPUMT_BROTLI_WIN_SCRATCH(n) ((size_t)4 * (n) + 256)
+int gpumt_brotli_win_depth(int level);
+int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
+				    size_t slot_stride, uint32_t *d_rec_len, int level, int stream);
 
 #define GPUMT_BROTLI_SCRATCH 825856u
 /* zstd decode: scratch per record (literals of one 128 KiB unit + 24576 sequences decoded ahead) */

@@ -1,0 +1,21 @@
+#!/bin/bash
+# Developer tool (CPU): gpumt_brotli_compress_batch_win's kernels under AddressSanitizer + UndefinedBehaviorSanitizer in a
+# stand-alone program (tests/emu/brotli_win_san.cpp) on the shape list of tests/brotli_win.py: encoded at two grids, decoded
+# by the emulated decoder kernels.
+set -e
+cd "$(dirname "$0")/.."
+A=${TMPDIR:-/tmp}/zmt_bwin_san; mkdir -p $A
+PYTHONPATH=$PWD:$PWD/tests:$PWD/tests/golden python -c "import brotli_win as W; print(W.dump_cases('$A/cases.bin'), 'cases')"
+SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
+H=zstdmt_amd/csrc/hip
+KERNELS=$(sed -n 's/^KERNELS := //p' tests/emu/Makefile)
+for k in $KERNELS; do
+  g++ -O1 -g -std=c++17 -DZMT_EMU $SAN -Itests/emu -I$H -w -x c++ -c $H/$k.hip -o $A/$k.o &
+done
+g++ -O1 -g -std=c++17 -DZMT_EMU $SAN -Itests/emu -I$H -w -c tests/emu/emu_runtime.cpp -o $A/emu_runtime.o &
+g++ -O1 -g -std=c++17 -DZMT_EMU $SAN -Itests/emu -I$H -w -c tests/emu/emu_api.cpp -o $A/emu_api.o &
+g++ -O1 -g -std=c++17 $SAN -c tests/emu/brotli_win_san.cpp -o $A/main.o &
+gcc -O1 -g -Wa,-Izstdmt_amd/csrc/data -c zstdmt_amd/csrc/host/brotli_static.c -o $A/brotli_static.o &
+wait
+g++ $SAN -o $A/brotli_win_san $A/main.o $A/emu_api.o $A/emu_runtime.o $A/brotli_static.o $(for k in $KERNELS; do echo $A/$k.o; done) -lpthread
+ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 $A/brotli_win_san $A/cases.bin

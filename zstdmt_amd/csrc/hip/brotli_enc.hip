@@ -21,6 +21,8 @@
  *                               every meta-block to a byte boundary, so the blocks of a chunk are
  *                               coded independently and concatenated; a block that does not shrink
  *                               becomes an uncompressed meta-block.
+ *   zmt_brotli_enc_win_kernel   the same body with the whole chunk as the match window (brotli_enc_win.h; opt-in, qualities
+ *                               9-11): candidates from a chain plane instead of the LDS table, WBITS by the chunk's length.
  *   zmt_brotli_assemble_kernel  one workgroup per chunk: 16-byte record header (hint = 64 KiB units the
  *                               decoder must provide, lib/brotli-mt_compress.c:294-304), the chunk's
  *                               blocks moved together, the final empty meta-block.
@@ -353,11 +355,18 @@ static __device__ __forceinline__ BeCmd be_command(const BEncLds &L, u32 ins, u3
 	return c;
 }
 
-template <int HLOG, u32 MM>
+#include "brotli_enc_win.h"
+
+/* WIN: the match finder is be_win_find over the chunk's chain plane (brotli_enc_win.h) instead of the LDS table; a candidate
+ * may then lie in an earlier block of the chunk (a block-relative position below 0, see ze_at), and block 0 declares the
+ * WBITS the chunk needs */
+template <int HLOG, u32 MM, bool WIN = false>
 static __device__ __forceinline__ void
 brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nblk_total, u32 blk_per_rec,
-		u8 *__restrict__ slots, u64 stride, u32 *__restrict__ blk_len, u8 *__restrict__ scratch)
+		u8 *__restrict__ slots, u64 stride, u32 *__restrict__ blk_len, u8 *__restrict__ scratch,
+		const u32 *__restrict__ plane = nullptr, u32 depth = 0)
 {
+	constexpr u32 NOCAND = WIN ? ZW_FAR : 0xFFFFFFFFu; /* "no candidate" among the block-relative positions */
 	const int lane = wv_lane();
 	/* 2^HLOG entries: runs on behind the struct for the larger tiers -- derived from the byte address of the enclosing
 	 * object, not from the member array (zstd_enc.hip has the reason) */
@@ -386,9 +395,14 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 		u8 *out = slots + (u64)rec * stride + BE_HDR + (u64)bi * BE_BSTRIDE;
 
 		/* ------------------------------------------------ match finding + greedy parse (zstd_enc.hip) */
-		for (u32 i = (u32)lane; i < (1u << HLOG); i += 64)
-			tab[i] = 0;
-		wv_sync();
+		if (!WIN) {
+			for (u32 i = (u32)lane; i < (1u << HLOG); i += 64)
+				tab[i] = 0;
+			wv_sync();
+		}
+		/* the stream header of block 0: "1" then WBITS - 17 in three bits; 18 for the table encoders, whose distances
+		 * stay inside a block */
+		const u32 wbits = WIN ? be_win_wbits(clen) : 18u;
 		u32 ns = 0, anchor = 0, cursor = 0;
 		u32 r_ll = 0, r_ml = 0, r_of = 0;
 		const u32 steps = bsize >= MM ? (bsize - MM) / 64 + 1 : 0;
@@ -404,6 +418,15 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 	do {                                                                                       \
 		const u32 p_ = (t) * 64u + (u32)lane;                                              \
 		const bool ok_ = (t) < steps && p_ + MM <= bsize;                                  \
+		if (WIN) {                                                                         \
+			/* the chain walk compares the input's bytes 8..23 itself: asked for here, where the  \
+			 * table encoders ask for them behind the lookup */                                  \
+			const u8 *iq_ = src + (ok_ ? p_ : 0u);                                     \
+			(M).d = ld64u(iq_ + 8);                                                    \
+			(M).e = ld64u(iq_ + 16);                                                   \
+			(Cc) = be_win_find<MM>(in + cstart, plane + cstart, bstart, bsize, p_, ok_, (V), (M).d, (M).e, \
+					       depth, (1u << wbits) - 16u);                                \
+		} else {                                                                           \
 		const u32 h_ = be_hash<HLOG>(V);                                                   \
 		const u32 e_ = ok_ ? tab[h_] : 0;                                                  \
 		wv_sync();                                                                         \
@@ -421,17 +444,20 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 		if (c_ >= p_)                                                                      \
 			c_ -= 65536u;                                                              \
 		(Cc) = (ok_ && c_ < p_) ? c_ : 0xFFFFFFFFu;                                        \
+		}                                                                                  \
 		/* 24 bytes of the candidate and of the input beyond the hashed 8: most matches are   \
 		 * measured right here, without the wave-wide extension below */                      \
 		{                                                                                  \
-			const u8 *cp_ = src + ((Cc) != 0xFFFFFFFFu ? (Cc) : 0u);                   \
+			const u8 *cp_ = ze_at<WIN>(src, (Cc) != NOCAND ? (Cc) : 0u);               \
 			const u8 *ip_ = src + (ok_ ? p_ : 0u);                                     \
 			(M).v = (V);                                                               \
 			(M).a = ld64u(cp_);                                                        \
 			(M).b = ld64u(cp_ + 8);                                                    \
 			(M).c = ld64u(cp_ + 16);                                                   \
-			(M).d = ld64u(ip_ + 8);                                                    \
-			(M).e = ld64u(ip_ + 16);                                                   \
+			if (!WIN) {                                                                \
+				(M).d = ld64u(ip_ + 8);                                            \
+				(M).e = ld64u(ip_ + 16);                                           \
+			}                                                                          \
 		}                                                                                  \
 	} while (0)
 		struct Cmp {
@@ -464,7 +490,7 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 					: x1 ? 8u + ((u32)__builtin_ctzll(x1) >> 3)
 					: x2 ? 16u + ((u32)__builtin_ctzll(x2) >> 3)
 					     : 24u;
-				const bool cand = c0 != 0xFFFFFFFFu && p >= cursor;
+				const bool cand = c0 != NOCAND && p >= cursor;
 				if (cand && m > bsize - p)
 					m = bsize - p;
 				u64 mask = wv_ballot(cand && m >= MM);
@@ -497,7 +523,7 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 							u32 k = 0;
 							bool stop = true;
 							if (pj + o < bsize) {
-								const u64 y = ld64u(src + pj + o) ^ ld64u(src + cj + o);
+								const u64 y = ld64u(src + pj + o) ^ ld64u(ze_at<WIN>(src, cj) + o);
 								k = y ? (u32)__builtin_ctzll(y) >> 3 : 8u;
 								stop = k < 8;
 							}
@@ -625,7 +651,7 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 		w.acc = 0;
 		w.n = 0;
 		if (bi == 0)
-			be_put(w, 3, 4, lane); /* WBITS = 18: "1" then 18 - 17 in three bits */
+			be_put(w, 1u | (wbits - 17u) << 1, 4, lane); /* WBITS: "1" then WBITS - 17 in three bits */
 		/* MLEN - 1 in 4 or 5 nibbles: the last nibble must not be zero (9.2) */
 		const u32 nib5 = bsize - 1 >= 65536u;
 		be_put(w, 0, 1, lane);                          /* ISLAST */
@@ -800,7 +826,7 @@ brotli_enc_body(BEncLds &L, const u8 *__restrict__ in, u64 n, u32 chunk, u32 nbl
 			w.acc = 0;
 			w.n = 0;
 			if (bi == 0)
-				be_put(w, 3, 4, lane);
+				be_put(w, 1u | (wbits - 17u) << 1, 4, lane);
 			be_put(w, 0, 1, lane);
 			be_put(w, nib5, 2, lane);
 			be_put(w, bsize - 1, nib5 ? 20 : 16, lane);
@@ -836,6 +862,14 @@ extern "C" __global__ void __launch_bounds__(64) zmt_brotli_enc_t3_kernel(BE_KER
 {
 	__shared__ __attribute__((aligned(16))) BEncLdsExt<14> S;
 	brotli_enc_body<14, 6u>(S.L, in, n, chunk, nblk_total, blk_per_rec, slots, stride, blk_len, scratch);
+}
+/* the whole-chunk window (qualities 9..11, opt-in): candidates from the chain plane of zmt_zstd_win_chain_kernel, `depth`
+ * per position; no hash table in LDS, the entropy-phase arrays alone (the 4 Ki-entry struct) */
+extern "C" __global__ void __launch_bounds__(64)
+zmt_brotli_enc_win_kernel(BE_KERNEL_ARGS, const u32 *__restrict__ plane, u32 depth)
+{
+	__shared__ __attribute__((aligned(16))) BEncLds L;
+	brotli_enc_body<BE_HLOG, 6u, true>(L, in, n, chunk, nblk_total, blk_per_rec, slots, stride, blk_len, scratch, plane, depth);
 }
 
 /* ---------------------------------------------------------------------------------------------
@@ -902,3 +936,71 @@ zmt_brotli_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__re
 		rec_len[rec] = at;
 	}
 }
+
+#ifdef ZMT_EMU
+/*
+ * TEST HARNESS ONLY (tests/emu compiles this file as host C++): gpumt_brotli_compress_batch_win over the fiber emulator, with
+ * the shapes of include/gpumt.h, so that the whole-chunk window and the host engine's GPUMT_BROTLI_WIN path run on the CPU.
+ * Synchronous, host pointers stand in for device pointers; the same argument checks as gpumt.hip.  Never part of the product.
+ */
+#include <vector>
+#include "../../../include/gpumt.h"
+extern "C" {
+void emu_brotli_compress_batch_level(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level);
+void emu_zstd_win_chain(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 grid); /* zstd_enc.hip: the one chain kernel */
+size_t emu_zstd_slot_stride(size_t chunk);
+
+int gpumt_brotli_win_depth(int level) { return level < 9 ? 0 : level == 9 ? 16 : level == 10 ? 32 : 64; }
+
+/* depth: 0 = by level.  cap: the scratch the "device" grants, 0 = any -- a request above it is refused and the call
+ * encodes with the table encoder of the quality, as below quality 9.  Returns the depth the window encoder ran with, 0
+ * where the table encoder ran */
+u32 emu_brotli_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level,
+				  u32 depth, u64 cap)
+{
+	const u32 nrec = n ? (u32)((n + chunk - 1) / chunk) : 1;
+	const u32 bpr = (chunk + BE_BLOCK - 1) / BE_BLOCK;
+	const u32 nblk = nrec * bpr;
+	if (!depth)
+		depth = (u32)gpumt_brotli_win_depth(level);
+	const u64 need = GPUMT_BROTLI_WIN_SCRATCH(n);
+	if (level < 9 || (cap && need > cap)) {
+		emu_brotli_compress_batch_level(in, n, chunk, slots, stride, rec_len, grid, level);
+		return 0;
+	}
+	if (grid > nblk)
+		grid = nblk;
+	std::vector<u32> blk_len(nblk, 0xA5A5A5A5u), plane((size_t)n + 1, 0xA5A5A5A5u);
+	std::vector<u8> seq((size_t)grid * BE_WSCRATCH, 0xA5);
+	u32 *bl = blk_len.data(), *pl = plane.data();
+	u8 *sq = seq.data();
+	emu_zstd_win_chain(in, n, chunk, pl, grid);
+	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_brotli_enc_win_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq, pl, depth); });
+	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_brotli_assemble_kernel(n, chunk, nrec, bpr, slots, stride, bl, rec_len); });
+	return depth;
+}
+
+/* (the emulated boundary keeps no variants: GPUMT_BROTLI_WIN_DEPTH and GPUMT_BROTLI_WIN_CAP -- bytes -- stand in for
+ * gpumt_set_variant's "brotli_win_depth" and "brotli_win_cap_mb") */
+int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
+				    uint32_t *d_rec_len, int level, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || chunk == 0 || chunk > 0x40000000u || slot_stride < emu_zstd_slot_stride(chunk) ||
+	    level < 0 || level > 11)
+		return GPUMT_E_ARG;
+	const char *e = getenv("GPUMT_BROTLI_WIN_DEPTH"), *c = getenv("GPUMT_BROTLI_WIN_CAP"), *t = getenv("GPUMT_TRACE");
+	const long dv = e && *e ? atol(e) : 0;
+	const u64 cap = c && *c ? strtoull(c, 0, 10) : 0;
+	if (dv < 0 || dv > 256)
+		return GPUMT_E_ARG;
+	const u32 ran = emu_brotli_compress_batch_win((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3, level,
+						      (u32)dv, cap);
+	if (t && atoi(t) >= 1 && level >= 9)
+		fprintf(stderr, "[gpumt brotli win] records %zu depth %u plane %zu fallback %d\n", n ? (n + chunk - 1) / chunk : (size_t)1, ran,
+			ran ? (size_t)4 * n : (size_t)0, ran ? 0 : 1);
+	return GPUMT_OK;
+}
+}
+#endif

@@ -111,6 +111,7 @@ __global__ void zmt_brotli_enc_t3_kernel(const u8 *, u64, u32, u32, u32, u8 *, u
 __global__ void zmt_snappy_enc_kernel(const u8 *, u64, u32, u32, u8 *, u64, u32 *);
 __global__ void zmt_snappy_dec_kernel(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *, const u32 *, u32 *, u32 *);
 __global__ void zmt_snappy_dec2_kernel(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *, const u32 *, u32 *, u32 *);
+__global__ void zmt_brotli_enc_win_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *, const u32 *, u32);
 __global__ void zmt_brotli_assemble_kernel(u64, u32, u32, u32, u8 *, u64, const u32 *, u32 *);
 __global__ void zmt_brotli_dec_kernel(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *, const u32 *,
 				      u32 *, u32 *, u8 *, const u8 *, u32);
@@ -180,6 +181,10 @@ struct gpumt_ctx {
 	int zwin_depth;   /* its candidates per position: 0 = by level (gpumt_zstd_win_depth), 1..256 = this many (A/B runs) */
 	int zwin_cap_mb;  /* 0 = none; else scratch requests of that call above this many MiB count as refused (the tests' way to the fallback) */
 	size_t zwin_refused; /* the smallest scratch of that call the device has refused (0 = none yet): not asked for again */
+	int bwin_waves;   /* the same four of the brotli encoder's window (gpumt_brotli_compress_batch_win, gpumt_brotli_win_depth) */
+	int bwin_depth;
+	int bwin_cap_mb;
+	size_t bwin_refused;
 	int trace;        /* GPUMT_TRACE */
 	int hc_waves;     /* developer: grid of the LZ4HC encoder (0 = GPUMT_LZ4HC_WAVES) */
 	int zdec_variant; /* 0 = small-table kernel, then general; 1 = general only */
@@ -1830,6 +1835,89 @@ int gpumt_brotli_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, 
 	return GPUMT_OK;
 }
 
+/* ---- the whole chunk as the match window (brotli_enc_win.h): the chain plane is the zstd encoder's ---- */
+int gpumt_brotli_win_depth(int level) { return level < 9 ? 0 : level == 9 ? 16 : level == 10 ? 32 : 64; }
+
+int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
+				    size_t slot_stride, uint32_t *d_rec_len, int level, int s)
+{
+	if (!h || !STREAM_OK(s) || chunk == 0 || chunk > 0x40000000u || slot_stride < gpumt_zstd_slot_stride(chunk) ||
+	    level < 0 || level > 11)
+		return GPUMT_E_ARG;
+	if (level < 9)
+		return gpumt_brotli_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, s);
+	if (use(h))
+		return GPUMT_E_HIP;
+	const size_t nrec = gpumt_lz4_record_count(n, chunk);
+	const u32 bpr = (u32)((chunk + ZE_BLOCK - 1) / ZE_BLOCK);
+	if (nrec * bpr > 0x7FFFFFFFu)
+		return GPUMT_E_ARG;
+	const u32 depth = h->bwin_depth ? (u32)h->bwin_depth : (u32)gpumt_brotli_win_depth(level);
+	if (!h->bwin_waves) {
+		int per_cu = 0;
+		CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, zmt_brotli_enc_win_kernel, 64, 0));
+		h->bwin_waves = (per_cu > 0 ? per_cu : 4) * (h->num_cus > 0 ? h->num_cus : 256);
+	}
+	/* slices of whole records, at most ZW_SLICE input bytes each; every slice sizes the same scratch */
+	const size_t rps = chunk >= ZW_SLICE ? 1 : ZW_SLICE / chunk, slice_rec = nrec < rps ? nrec : rps;
+	const size_t slice_in = slice_rec * chunk < n ? slice_rec * chunk : n, slice_blk = slice_rec * bpr;
+	const size_t egrid = slice_blk < (size_t)h->bwin_waves ? slice_blk : (size_t)h->bwin_waves;
+	const size_t cwaves = (size_t)4 * (h->num_cus > 0 ? h->num_cus : 256), cgrid = slice_rec < cwaves ? slice_rec : cwaves;
+	const size_t o_seq = (slice_blk * 4 + 255) & ~(size_t)255;
+	const size_t o_head = o_seq + ((egrid * ((size_t)3 * ZE_MAXSEQ * 4) + 255) & ~(size_t)255);
+	const size_t o_plane = o_head + (cgrid * 4 << ZW_HLOG_MAX);
+	const size_t need = (o_plane + GPUMT_BROTLI_WIN_SCRATCH(slice_in) + 0xFFFFF) & ~(size_t)0xFFFFF;
+	int win = !(h->bwin_refused && need >= h->bwin_refused);
+	if (win && h->bwin_cap_mb && need > ((size_t)h->bwin_cap_mb << 20)) {
+		h->bwin_refused = need;
+		win = 0;
+	}
+	if (win && need > h->scratch_bytes[0][s]) {
+		/* ask before letting go of the area the stream has: a refusal must leave the table encoder its scratch */
+		void *p = dev_alloc(h, need);
+		if (!p) {
+			(void)hipGetLastError(); /* (a refused allocation is no error of this call) */
+			h->bwin_refused = need;
+			win = 0;
+		} else {
+			if (h->scratch[0][s]) {
+				if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+					dev_free(h, p);
+					return GPUMT_E_HIP;
+				}
+				dev_free(h, h->scratch[0][s]);
+			}
+			h->scratch[0][s] = p;
+			h->scratch_bytes[0][s] = need;
+		}
+	}
+	if (h->trace >= 1)
+		fprintf(stderr, "[gpumt brotli win] records %zu depth %u plane %zu fallback %d\n", nrec, win ? depth : 0u,
+			win ? (size_t)4 * slice_in : (size_t)0, win ? 0 : 1);
+	if (!win)
+		return gpumt_brotli_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, s);
+	u32 *blk_len = (u32 *)h->scratch[0][s];
+	u8 *seqbuf = (u8 *)h->scratch[0][s] + o_seq;
+	u32 *heads = (u32 *)((u8 *)h->scratch[0][s] + o_head), *plane = (u32 *)((u8 *)h->scratch[0][s] + o_plane);
+	PROF0(9);
+	for (size_t r0 = 0; r0 < nrec; r0 += slice_rec) {
+		const size_t nr = nrec - r0 < slice_rec ? nrec - r0 : slice_rec, i0 = r0 * chunk;
+		const size_t ni = n - i0 < nr * chunk ? n - i0 : nr * chunk, nb = nr * bpr;
+		const unsigned eg = (unsigned)(nb < egrid ? nb : egrid), cg = (unsigned)(nr < cgrid ? nr : cgrid);
+		const u8 *in = (const u8 *)d_in + i0;
+		u8 *slots = (u8 *)d_slots + r0 * slot_stride;
+		hipLaunchKernelGGL(zmt_zstd_win_chain_kernel, dim3(cg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nr, plane,
+				   heads);
+		hipLaunchKernelGGL(zmt_brotli_enc_win_kernel, dim3(eg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nb, bpr,
+				   slots, (u64)slot_stride, blk_len, seqbuf, (const u32 *)plane, depth);
+		hipLaunchKernelGGL(zmt_brotli_assemble_kernel, dim3((unsigned)nr), dim3(256), 0, h->st[s], (u64)ni, (u32)chunk, (u32)nr,
+				   bpr, slots, (u64)slot_stride, (const u32 *)blk_len, d_rec_len + r0);
+	}
+	PROF1(9);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
 extern "C" const unsigned char zmt_brotli_static[], zmt_brotli_static_end[];
 
 int gpumt_brotli_decompress_batch(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off,
@@ -2022,6 +2110,17 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 		prev = h->zwin_cap_mb;
 		h->zwin_cap_mb = variant;
 		h->zwin_refused = 0; /* (a new cap: ask again) */
+	} else if (!strcmp(what, "brotli_win_depth")) {
+		if (variant < 0 || variant > 256)
+			return -1;
+		prev = h->bwin_depth;
+		h->bwin_depth = variant;
+	} else if (!strcmp(what, "brotli_win_cap_mb")) {
+		if (variant < 0)
+			return -1;
+		prev = h->bwin_cap_mb;
+		h->bwin_cap_mb = variant;
+		h->bwin_refused = 0; /* (a new cap: ask again) */
 	} else if (!strcmp(what, "lz4_run_par")) {
 		if (variant != 0 && variant != 1)
 			return -1;

@@ -22,23 +22,13 @@
 #ifndef ZMT_ZSTD_ENC_WIN_H
 #define ZMT_ZSTD_ENC_WIN_H
 
-#define ZW_NONE 0xFFFFFFFFu
-#define ZW_FAR 0x80000000u
-#define ZW_HLOG_MAX 17           /* head table: min(17, log2(chunk) - 3) bits, at least ZW_HLOG_MIN */
-#define ZW_HLOG_MIN 12
+#include "enc_win_common.h" /* ZW_NONE, ZW_FAR, ZW_HLOG_*, ze_at: shared with the brotli encoder's window */
 #define ZW_MAXDIST (1u << 27)    /* offset codes <= 27: what the predefined offset table covers */
-#define ZW_HEAD_BYTES (4u << ZW_HLOG_MAX) /* per resident wave of the chain kernel */
 
 static __device__ __forceinline__ u32 zw_hlog(u32 clen)
 {
 	const int l = 31 - __builtin_clz(clen | 1u) - 3;
 	return (u32)(l > ZW_HLOG_MAX ? ZW_HLOG_MAX : l < ZW_HLOG_MIN ? ZW_HLOG_MIN : l);
-}
-
-/* base + a block-relative position that may be negative (WIN) */
-template <bool WIN> static __device__ __forceinline__ const u8 *ze_at(const u8 *base, u32 rel)
-{
-	return WIN ? base + (ptrdiff_t)(int)rel : base + rel;
 }
 
 extern "C" __global__ void __launch_bounds__(64)

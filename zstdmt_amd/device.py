@@ -407,10 +407,14 @@ class Engine:
                                                     int(out_bytes), d_out_off.ptr, d_out_len.ptr,
                                                     d_status.ptr, stream), "zstd_decompress_batch")
 
-    def brotli_compress(self, d_in, n, chunk, d_slots, stride, d_rec_len, stream=0, level=1):
-        self._ck(self.L.gpumt_brotli_compress_batch_level(self.h, d_in.ptr, int(n), int(chunk), d_slots.ptr,
-                                                          int(stride), d_rec_len.ptr, int(level), stream),
-                 "brotli_compress_batch_level")
+    def brotli_compress(self, d_in, n, chunk, d_slots, stride, d_rec_len, stream=0, level=1, win=False):
+        """win=True: gpumt_brotli_compress_batch_win, the whole chunk as the match window from quality 9 on"""
+        call = self.L.gpumt_brotli_compress_batch_win if win else self.L.gpumt_brotli_compress_batch_level
+        self._ck(call(self.h, d_in.ptr, int(n), int(chunk), d_slots.ptr, int(stride), d_rec_len.ptr, int(level), stream),
+                 "brotli_compress_batch_win" if win else "brotli_compress_batch_level")
+
+    def brotli_win_depth(self, level):
+        return int(self.L.gpumt_brotli_win_depth(int(level)))
 
     def brotli_decompress(self, d_stream, d_rec_off, d_rec_len, nrec, d_out, d_out_off, d_out_cap, d_out_len,
                           d_status, stream=0):
@@ -464,8 +468,8 @@ class Engine:
 
     # ---- convenience round trips on host bytes (tests) ----------------------------------------
     def compress_bytes(self, data: bytes, chunk: int, codec="lz4", level=1, win=False):
-        """-> (stream bytes, rec_off[n+1] u64, rec_len[n] u32); win: codec "zstd" with the whole-chunk window"""
-        assert not win or codec == "zstd"
+        """-> (stream bytes, rec_off[n+1] u64, rec_len[n] u32); win: codec "zstd" or "brotli" with the whole-chunk window"""
+        assert not win or codec in ("zstd", "brotli")
         n = len(data)
         nrec = self.record_count(n, chunk)
         stride = self.zstd_slot_stride(chunk) if codec in ("zstd", "brotli") else self.slot_stride(chunk)
@@ -477,7 +481,7 @@ class Engine:
             if codec == "zstd":
                 self.zstd_compress(d_in, n, chunk, d_slots, stride, d_len, level=level, win=win)
             elif codec == "brotli":
-                self.brotli_compress(d_in, n, chunk, d_slots, stride, d_len, level=level)
+                self.brotli_compress(d_in, n, chunk, d_slots, stride, d_len, level=level, win=win)
             else:
                 self.lz4_compress(d_in, n, chunk, d_slots, stride, d_len, level=level)
             rec_len = self.download(d_len, nrec * 4, np.uint32)
