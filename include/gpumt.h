@@ -384,6 +384,56 @@ int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t strea
 				uint32_t *d_out_len, uint32_t *d_status, int stream);
 
 /*
+ * gpumt_zstd_decompress_batch with the records of several blocks decoded block-parallel (opt-in; what GPUMT_ZSTD_REC_PAR=1
+ * makes ZSTDCB_decompressDCtx call).  Same arguments and slack rule, and for every record the same status, the same
+ * d_out_len and the same output bytes: a frame without a content size passes a capacity and gets the decoded size back, a
+ * record whose d_status is not GPUMT_ST_OK on entry is not visited, and nothing outside a record's
+ * [d_out_off[i], d_out_off[i] + d_out_len[i]) is written.  d_rec_par (nrec words, may be NULL) receives per record the
+ * number of its blocks whose result came from the block call (gpumt_zstd_decompress_blocks_par on the tables made here) and
+ * was kept, 0 for every other record.  It says that the record went through that call, not which of that call's own routes
+ * decoded it: the call leaves a run to its entropy stage or to its serial wave by its own rules (a run of one block, a
+ * serial prefix, GPUMT_ZSTD_RUN_PAR=0 / GPUMT_ZSTD_RUN_PRE=0, a refused origin plane), with the same bytes.
+ * A return value other than GPUMT_OK (the block call or the record decoders failed to launch) leaves the batch undefined:
+ * d_status may not have been written, and d_out_len of records without a stated size may already hold decoded sizes.
+ * The stages, stream-ordered, none of which waits on another wave:
+ *   count   one lane per OK record checks the 12-byte header and the frame header (magic, descriptor, reserved bit,
+ *           Window_Descriptor, Dictionary_ID, Frame_Content_Size) and hops from block header to block header until
+ *           Last_Block, the end of the record or a block that would leave it.  A record is eligible when the walk ended on
+ *           Last_Block, the frame has no Dictionary_ID field, a stated content size equals d_out_len[i], and it has
+ *           zstd_rec_min_blocks .. 65536 blocks.  The stage decides no verdict.
+ *   (host)  one copy of the counts to pinned memory and one hipStreamSynchronize of `stream`: the host cuts the batch into
+ *           slices of consecutive records with at most 4096 eligible records, zstd_rec_slice_blocks blocks (a record of
+ *           more is a slice of its own) and 0xFFFFFFF0 stream bytes.  A batch without an eligible record goes to the record
+ *           decoders as it is.  A slice passes d_stream and d_out offset to its first eligible record (rounded down to 256), so
+ *           the origin plane of the block call is 4 x the slice's output span.
+ *   table   per slice a scan of the block counts, then one lane per eligible record writes its gpumt_zstd_block entries and
+ *           one gpumt_zstd_run (hist 0, GPUMT_ZRUN_FIRST | GPUMT_ZRUN_LAST, carry 0, out_cap = d_out_len[i]).
+ *   blocks  gpumt_zstd_decompress_blocks_par on the slice's tables, unchanged: it falls back by its own rules.
+ *   finish  one lane per eligible record keeps it when the run's status is OK, its length is the stated content size, and
+ *           behind the last block lie exactly the 4 checksum bytes the descriptor promises, or nothing.  A kept record
+ *           gets d_out_len (no stated size), d_rec_par, its checksum words, and a skip value in a scratch copy of d_status.
+ *   records the record decoders of gpumt_zstd_decompress_batch over the whole batch with that scratch copy: records that
+ *           were not eligible or not kept are decoded and judged there, so the verdicts are the serial call's by
+ *           construction.  A merge writes d_status (OK for kept records, else the decoders' word) and the XXH64 verify runs
+ *           once over all records.
+ * Internal scratch: areas of its own, which the block call and the record decoders do not replace -- 76 bytes per record
+ * and, for the largest slice, 16 bytes per block and 40 per eligible record, plus 2 x GPUMT_ZSTD_CARRY_BYTES -- next to
+ * theirs.  If the device refuses them the call is gpumt_zstd_decompress_batch (d_rec_par 0) and that size is not asked for
+ * again.
+ * gpumt_set_variant: "zstd_rec_par" 1 = default, 0 = the call is gpumt_zstd_decompress_batch with d_rec_par all 0;
+ * "zstd_rec_min_blocks" 1..65536 (default 4: a placeholder, not a measurement; GPUMT_ZSTD_REC_MIN_BLOCKS);
+ * "zstd_rec_slice_blocks" 2..65536 (default 4096; GPUMT_ZSTD_REC_SLICE_BLOCKS); "zstd_rec_cap_mb" (0 = none) refuses the
+ * stage's own scratch above that many MiB, the tests' way to the fallback.  Values out of range are refused with -1 and
+ * change nothing.  With GPUMT_TRACE=1 every call prints `[gpumt zstd rec] records N par P blocks B slices S fallback F`
+ * (P eligible records with B blocks in S calls of the block stages; F = 1: this stage's own scratch was refused and the
+ * record decoders took the whole batch -- the block call's own fallbacks are not counted here).
+ */
+int gpumt_zstd_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				    const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
+				    void *d_out, size_t out_bytes, const uint64_t *d_out_off,
+				    uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int stream);
+
+/*
  * Block-level zstd decode: what the plain .zst path of ZSTDCB_decompressDCtx uses in place of one record per frame
  * (replaces the streaming ZSTD_decompressStream of st_decompress, lib/zstd-mt_decompress.c:552-687).  The caller walks the
  * frame and block headers and passes a table of blocks and a list of runs; a run is the consecutive blocks of one frame

@@ -17,6 +17,10 @@ typedef uint16_t u16;
 typedef uint32_t u32;
 typedef uint64_t u64;
 
+/* record layout and slice rule of gpumt_zstd_decompress_batch_par */
+#define ZREC_HOST_ONLY
+#include "zstd_dec_rec.h"
+
 extern "C" {
 __global__ void zmt_xxh32_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *, const u32 *,
 				 const u32 *, u32 *);
@@ -60,6 +64,15 @@ __global__ void zmt_zstd_par_fallback_kernel(const u8 *, u64, const gpumt_zstd_b
 					     u64, u8 *, u32 *, u32 *, u8 *, const u32 *, const u32 *, const u8 *, ZPar);
 __global__ void zmt_zstd_par_carry_kernel(const u8 *, u64, const gpumt_zstd_block *, u32, const gpumt_zstd_run *, u32,
 					  const void *, u8 *, u32 *, u32 *, u32 *, ZPar);
+/* the record stage in front of it (zstd_dec_rec.h) */
+__global__ void zmt_zstd_rec_count_kernel(const u8 *, u64, const u64 *, const u32 *, u32, const u64 *, const u32 *, u64,
+					  const u32 *, u32, ZRec *);
+__global__ void zmt_zstd_rec_scan_kernel(const ZRec *, u32, u32 *, u32 *);
+__global__ void zmt_zstd_rec_table_kernel(const u8 *, const ZRec *, u32, const u32 *, const u32 *, u64, u64, u32, u32,
+					  gpumt_zstd_block *, gpumt_zstd_run *);
+__global__ void zmt_zstd_rec_finish_kernel(const u8 *, const ZRec *, u32, const u32 *, u32, const u32 *, const u32 *, u32 *,
+					   u32 *, u32 *, u32 *, u32 *);
+__global__ void zmt_zstd_rec_merge_kernel(const u32 *, u32, u32 *);
 /* scratch of gpumt_lz4_decompress_blocks_par (lz4_dec_par.h) */
 struct Lz4Par {
 	u16 *origin;
@@ -193,6 +206,17 @@ struct gpumt_ctx {
 	size_t zrun_pre_refused; /* the smallest pre-pass scratch the device has refused (0 = none yet): not asked for again */
 	int zrun_par;     /* 1 = block-parallel execute stage behind it (gpumt_zstd_decompress_blocks_par); 0 = none */
 	size_t zrun_par_refused; /* the same for that stage's scratch */
+	int zrec_par;     /* 1 = multi-block records through the block stages (gpumt_zstd_decompress_batch_par); 0 = the record decoders alone */
+	int zrec_min_blocks;   /* records of fewer blocks stay with the record decoders */
+	int zrec_slice_blocks; /* blocks per call of the block stages */
+	int zrec_cap_mb;  /* 0 = none; else that stage's own scratch above this many MiB counts as refused (the tests' way to the fallback) */
+	size_t zrec_refused; /* the smallest such scratch the device has refused (0 = none yet): not asked for again */
+	void *zrec_area[GPUMT_NSTREAMS]; /* that stage's own device scratch: the block calls and the record decoders replace scratch[1] */
+	size_t zrec_bytes[GPUMT_NSTREAMS];
+	void *zrec_tab[GPUMT_NSTREAMS];  /* ... and its tables per slice, sized once the counts are known */
+	size_t zrec_tab_bytes[GPUMT_NSTREAMS];
+	void *zrec_pin[GPUMT_NSTREAMS]; /* pinned copy of the per-record counts, for the host to cut slices */
+	size_t zrec_pin_bytes[GPUMT_NSTREAMS];
 	int lrun_par;     /* 1 = linked runs of plain .lz4 blocks side by side (gpumt_lz4_decompress_blocks_par); 0 = one wave per run */
 	size_t lrun_par_refused; /* the smallest origin-plane scratch the device has refused (0 = none yet): not asked for again */
 	int lblk_seg;     /* 1 = plain .lz4 blocks in segments side by side (gpumt_lz4_decompress_blocks_seg); 0 = one wave per run */
@@ -368,6 +392,22 @@ int gpumt_open(int device, gpumt_ctx **out)
 			else
 				fprintf(stderr, "gpumt: GPUMT_ZSTD_RUN_PAR=%s ignored (0 or 1)\n", e);
 		}
+		/* gpumt_zstd_decompress_batch_par: GPUMT_ZSTD_REC_MIN_BLOCKS (1..65536) and GPUMT_ZSTD_REC_SLICE_BLOCKS (2..65536) */
+		h->zrec_par = 1;
+		h->zrec_min_blocks = 4;
+		h->zrec_slice_blocks = 4096;
+		for (int k = 0; k < 2; k++) {
+			const char *name = k ? "GPUMT_ZSTD_REC_SLICE_BLOCKS" : "GPUMT_ZSTD_REC_MIN_BLOCKS";
+			e = getenv(name);
+			if (e && *e) {
+				char *end;
+				const long v = strtol(e, &end, 10);
+				if (*end || v < (k ? 2 : 1) || v > 65536)
+					fprintf(stderr, "gpumt: %s=%s ignored (%d..65536)\n", name, e, k ? 2 : 1);
+				else
+					*(k ? &h->zrec_slice_blocks : &h->zrec_min_blocks) = (int)v;
+			}
+		}
 		/* GPUMT_LZ4_RUN_PAR=0: gpumt_lz4_decompress_blocks_par decodes every run with one wave */
 		e = getenv("GPUMT_LZ4_RUN_PAR");
 		h->lrun_par = 1;
@@ -412,6 +452,14 @@ void gpumt_close(gpumt_ctx *h)
 		for (int i = 0; i < GPUMT_NSTREAMS; i++)
 			if (h->scratch[k][i])
 				dev_free(h, h->scratch[k][i]);
+	for (int i = 0; i < GPUMT_NSTREAMS; i++) {
+		if (h->zrec_area[i])
+			dev_free(h, h->zrec_area[i]);
+		if (h->zrec_tab[i])
+			dev_free(h, h->zrec_tab[i]);
+		if (h->zrec_pin[i])
+			(void)hipHostFree(h->zrec_pin[i]);
+	}
 	for (int i = 0; i < NTIMERS; i++) {
 		(void)hipEventDestroy(h->t0[i]);
 		(void)hipEventDestroy(h->t1[i]);
@@ -1493,15 +1541,14 @@ static size_t zseq_pad(void)
 	return (size_t)v;
 }
 
-int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
-				const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
-				void *d_out, size_t out_bytes, const uint64_t *d_out_off,
-				uint32_t *d_out_len, uint32_t *d_status, int s)
+/* The record decoders over the records whose `status` word is GPUMT_ST_OK.  gpumt_zstd_decompress_batch passes d_status and
+ * no checksum words: they lie in the scratch and the verify pass follows.  gpumt_zstd_decompress_batch_par passes its
+ * scratch copy of the status array and checksum words of its own (x_chk_e / x_chk_v), and runs the verify pass itself. */
+static int zstd_decompress_records(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				   const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				   const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, u32 *x_chk_e, u32 *x_chk_v,
+				   int s)
 {
-	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
-		return GPUMT_E_ARG;
-	if (use(h))
-		return GPUMT_E_HIP;
 	/* per-record scratch (literals + sequences decoded ahead) is what bounds a launch: records go
 	 * in slices of at most ZD_SLICE (5 GiB of scratch), each slice still 4x the resident waves */
 	const size_t ZD_SLICE = 16384;
@@ -1514,7 +1561,7 @@ int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t strea
 	const size_t seq_bytes = seq_on ? out_bytes + 32 : 0;
 	if (want_scratch(h, 1, s, lit_bytes + chk_bytes + seq_bytes))
 		return GPUMT_E_HIP;
-	u32 *chk_e = (u32 *)((u8 *)h->scratch[1][s] + lit_bytes), *chk_v = chk_e + nrec;
+	u32 *chk_e = x_chk_e ? x_chk_e : (u32 *)((u8 *)h->scratch[1][s] + lit_bytes), *chk_v = x_chk_e ? x_chk_v : chk_e + nrec;
 	/* the region's capacity goes to both kernels (zstd_dec_seq.h): records whose [out_off, out_off + out_len) does not fit
 	 * out_bytes are decoded without the pre-pass instead of writing past the scratch */
 	u8 *seqbuf = seq_on ? (u8 *)h->scratch[1][s] + lit_bytes + chk_bytes + 16 : NULL;
@@ -1551,12 +1598,26 @@ int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t strea
 		}
 	}
 	/* XXH64 content checksums, for the frames that carry one */
-	hipLaunchKernelGGL(zmt_xxh64_verify_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), dim3(256), 0,
-			   h->st[s], (const u8 *)d_out, d_out_off, (const u32 *)d_out_len, (u32)nrec, (const u32 *)chk_e,
-			   (const u32 *)chk_v, d_status);
+	if (!x_chk_e)
+		hipLaunchKernelGGL(zmt_xxh64_verify_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), dim3(256), 0,
+				   h->st[s], (const u8 *)d_out, d_out_off, (const u32 *)d_out_len, (u32)nrec, (const u32 *)chk_e,
+				   (const u32 *)chk_v, d_status);
 	PROF1(11);
 	CK(hipGetLastError());
 	return GPUMT_OK;
+}
+
+int gpumt_zstd_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
+				void *d_out, size_t out_bytes, const uint64_t *d_out_off,
+				uint32_t *d_out_len, uint32_t *d_status, int s)
+{
+	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	return zstd_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+				       d_out_len, d_status, NULL, NULL, s);
 }
 
 int gpumt_zstd_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
@@ -1753,6 +1814,159 @@ int gpumt_zstd_decompress_blocks_par(gpumt_ctx *h, const void *d_stream, size_t 
 	if (d_block_mark)
 		CK(hipMemcpyAsync(d_block_mark, mark, nblk * 4, hipMemcpyDeviceToDevice, st));
 	PROF1(11);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
+/* grow one of the record stage's areas (never shrinks): the larger area first, the current one dropped only once it is
+ * there.  -> nonzero when the device refuses */
+static int zrec_want(gpumt_ctx *h, void **area, size_t *have, size_t bytes, hipStream_t st)
+{
+	if (bytes <= *have)
+		return 0;
+	bytes = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
+	void *p = dev_alloc(h, bytes);
+	if (!p) {
+		(void)hipGetLastError(); /* (a refused allocation is no error of the call) */
+		return 1;
+	}
+	if (*area) {
+		if (hipStreamSynchronize(st) != hipSuccess) {
+			dev_free(h, p);
+			return 1;
+		}
+		dev_free(h, *area);
+	}
+	*area = p;
+	*have = bytes;
+	return 0;
+}
+
+int gpumt_zstd_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				    const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				    const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int s)
+{
+	static_assert(sizeof(ZRec) == 56, "record layout");
+	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	const hipStream_t st = h->st[s];
+	if (d_rec_par)
+		CK(hipMemsetAsync(d_rec_par, 0, nrec * 4, st));
+	if (!h->zrec_par) {
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt zstd rec] records %zu par 0 blocks 0 slices 0 fallback 0\n", nrec);
+		return zstd_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					       d_out_len, d_status, NULL, NULL, s);
+	}
+	/* the stage's own areas, which the block call and the record decoders do not replace.  Per record: the counts and five
+	 * words (scratch status, checksum expected / valid, first block, run).  Per slice, sized once the counts are known: the
+	 * block table, the run table with length and status per run, and a carry area no run touches */
+	const size_t rec_bytes = (nrec * sizeof(ZRec) + 255) & ~(size_t)255, word_bytes = (nrec * 4 + 255) & ~(size_t)255;
+	const size_t need_a = rec_bytes + 5 * word_bytes;
+	const size_t cap = h->zrec_cap_mb ? (size_t)h->zrec_cap_mb << 20 : ~(size_t)0;
+	int par = !(h->zrec_refused && need_a >= h->zrec_refused);
+	if (par && need_a > cap) {
+		h->zrec_refused = need_a;
+		par = 0;
+	}
+	if (par && zrec_want(h, &h->zrec_area[s], &h->zrec_bytes[s], need_a, st)) {
+		h->zrec_refused = need_a;
+		par = 0;
+	}
+	if (par && rec_bytes > h->zrec_pin_bytes[s]) {
+		/* (the copy that read the old area was waited for by the call that queued it) */
+		void *p = NULL;
+		if (hipHostMalloc(&p, rec_bytes, hipHostMallocDefault) != hipSuccess || !p) {
+			(void)hipGetLastError();
+			h->zrec_refused = need_a;
+			par = 0;
+		} else {
+			if (h->zrec_pin[s])
+				(void)hipHostFree(h->zrec_pin[s]);
+			h->zrec_pin[s] = p;
+			h->zrec_pin_bytes[s] = rec_bytes;
+		}
+	}
+	if (!par) {
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt zstd rec] records %zu par 0 blocks 0 slices 0 fallback 1\n", nrec);
+		return zstd_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					       d_out_len, d_status, NULL, NULL, s);
+	}
+	u8 *area = (u8 *)h->zrec_area[s];
+	ZRec *recs = (ZRec *)area;
+	u32 *sstatus = (u32 *)(area + rec_bytes), *chk_e = (u32 *)((u8 *)sstatus + word_bytes);
+	u32 *chk_v = (u32 *)((u8 *)chk_e + word_bytes), *rfirst = (u32 *)((u8 *)chk_v + word_bytes);
+	u32 *rrun = (u32 *)((u8 *)rfirst + word_bytes);
+	const u8 *stream = (const u8 *)d_stream;
+	const dim3 per_rec((unsigned)((nrec + 255) / 256)), tpb(256);
+	hipLaunchKernelGGL(zmt_zstd_rec_count_kernel, per_rec, tpb, 0, st, stream, (u64)stream_bytes, d_rec_off, d_rec_len, (u32)nrec,
+			   d_out_off, (const u32 *)d_out_len, (u64)out_bytes, (const u32 *)d_status, (u32)h->zrec_min_blocks, recs);
+	/* one round trip: the host sizes the tables and the launches of the block stages from the counts */
+	const ZRec *hrec = (const ZRec *)h->zrec_pin[s];
+	CK(hipMemcpyAsync(h->zrec_pin[s], recs, nrec * sizeof(ZRec), hipMemcpyDeviceToHost, st));
+	CK(hipStreamSynchronize(st));
+	const u32 SB = (u32)h->zrec_slice_blocks;
+	size_t npar = 0, nblocks = 0, nslices = 0, max_blk = 0, max_run = 0;
+	ZRecSlice S;
+	for (size_t at = 0; zrec_next_slice(hrec, nrec, at, SB, &S); at = S.b) {
+		npar += S.nrun;
+		nblocks += S.nblk;
+		nslices++;
+		max_blk = S.nblk > max_blk ? S.nblk : max_blk;
+		max_run = S.nrun > max_run ? S.nrun : max_run;
+	}
+	const size_t blk_bytes = (max_blk * sizeof(gpumt_zstd_block) + 255) & ~(size_t)255;
+	const size_t run_bytes = (max_run * (sizeof(gpumt_zstd_run) + 8) + 255) & ~(size_t)255;
+	const size_t need_b = blk_bytes + run_bytes + 2 * (size_t)GPUMT_ZSTD_CARRY_BYTES, need = need_a + need_b;
+	if (nslices && ((h->zrec_refused && need >= h->zrec_refused) || need > cap ||
+			zrec_want(h, &h->zrec_tab[s], &h->zrec_tab_bytes[s], need_b, st))) {
+		h->zrec_refused = need;
+		par = 0;
+	}
+	if (!par || !nslices) {
+		/* nothing for the block stages (or no room for their tables): the record decoders, on d_status itself */
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt zstd rec] records %zu par 0 blocks 0 slices 0 fallback %d\n", nrec, par ? 0 : 1);
+		return zstd_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					       d_out_len, d_status, NULL, NULL, s);
+	}
+	gpumt_zstd_block *blocks = (gpumt_zstd_block *)h->zrec_tab[s];
+	gpumt_zstd_run *runs = (gpumt_zstd_run *)((u8 *)blocks + blk_bytes);
+	u32 *run_len = (u32 *)(runs + max_run), *run_st = run_len + max_run;
+	u8 *carry = (u8 *)blocks + blk_bytes + run_bytes;
+	CK(hipMemcpyAsync(sstatus, d_status, nrec * 4, hipMemcpyDeviceToDevice, st));
+	CK(hipMemsetAsync(chk_v, 0, nrec * 4, st));
+	for (size_t at = 0; zrec_next_slice(hrec, nrec, at, SB, &S); at = S.b) {
+		const u32 n = (u32)(S.b - S.a);
+		hipLaunchKernelGGL(zmt_zstd_rec_scan_kernel, dim3(1), tpb, 0, st, (const ZRec *)(recs + S.a), n, rfirst + S.a,
+				   rrun + S.a);
+		hipLaunchKernelGGL(zmt_zstd_rec_table_kernel, dim3((n + 255) / 256), tpb, 0, st, stream, (const ZRec *)(recs + S.a), n,
+				   (const u32 *)(rfirst + S.a), (const u32 *)(rrun + S.a), S.in_lo, S.out_lo, S.nblk, S.nrun, blocks,
+				   runs);
+		/* the existing call, with d_stream and d_out at the slice: its origin plane is 4 x the slice's output span */
+		const int rc = gpumt_zstd_decompress_blocks_par(h, stream + S.in_lo, (size_t)(S.in_hi - S.in_lo), blocks, S.nblk, runs,
+								S.nrun, (u8 *)d_out + S.out_lo, (size_t)(S.out_hi - S.out_lo), carry,
+								run_len, run_st, NULL, NULL, s);
+		if (rc != GPUMT_OK)
+			return rc;
+		hipLaunchKernelGGL(zmt_zstd_rec_finish_kernel, dim3((n + 255) / 256), tpb, 0, st, stream, (const ZRec *)(recs + S.a), n,
+				   (const u32 *)(rrun + S.a), S.nrun, (const u32 *)run_len, (const u32 *)run_st, d_out_len + S.a,
+				   d_rec_par ? d_rec_par + S.a : (u32 *)NULL, sstatus + S.a, chk_e + S.a, chk_v + S.a);
+	}
+	if (h->trace >= 1)
+		fprintf(stderr, "[gpumt zstd rec] records %zu par %zu blocks %zu slices %zu fallback 0\n", nrec, npar, nblocks,
+			nslices);
+	/* everything the block stages did not keep is decoded and judged by the record decoders */
+	const int rc = zstd_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					       d_out_len, sstatus, chk_e, chk_v, s);
+	if (rc != GPUMT_OK)
+		return rc;
+	hipLaunchKernelGGL(zmt_zstd_rec_merge_kernel, per_rec, tpb, 0, st, (const u32 *)sstatus, (u32)nrec, d_status);
+	hipLaunchKernelGGL(zmt_xxh64_verify_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), tpb, 0, st, (const u8 *)d_out,
+			   d_out_off, (const u32 *)d_out_len, (u32)nrec, (const u32 *)chk_e, (const u32 *)chk_v, d_status);
 	CK(hipGetLastError());
 	return GPUMT_OK;
 }
@@ -2099,6 +2313,27 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 			return -1;
 		prev = h->zrun_par;
 		h->zrun_par = variant;
+	} else if (!strcmp(what, "zstd_rec_par")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->zrec_par;
+		h->zrec_par = variant;
+	} else if (!strcmp(what, "zstd_rec_min_blocks")) {
+		if (variant < 1 || variant > 65536)
+			return -1;
+		prev = h->zrec_min_blocks;
+		h->zrec_min_blocks = variant;
+	} else if (!strcmp(what, "zstd_rec_slice_blocks")) {
+		if (variant < 2 || variant > 65536)
+			return -1;
+		prev = h->zrec_slice_blocks;
+		h->zrec_slice_blocks = variant;
+	} else if (!strcmp(what, "zstd_rec_cap_mb")) {
+		if (variant < 0)
+			return -1;
+		prev = h->zrec_cap_mb;
+		h->zrec_cap_mb = variant;
+		h->zrec_refused = 0; /* (a new cap: ask again) */
 	} else if (!strcmp(what, "zstd_win_depth")) {
 		if (variant < 0 || variant > 256)
 			return -1;

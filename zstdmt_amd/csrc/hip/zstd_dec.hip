@@ -2099,6 +2099,7 @@ zmt_zstd_dec_run_pre_kernel(const u8 *__restrict__ stream, u64 stream_bytes, con
 }
 
 #include "zstd_dec_par.h"
+#include "zstd_dec_rec.h"
 
 /* ------------------------------------------------------------------ XXH64 content checksum
  * Four lanes per record = the four accumulators of XXH64 (one 32-byte stripe per step); only records
@@ -2568,6 +2569,128 @@ int gpumt_xxh64_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const
 		return GPUMT_E_ARG;
 	if (njobs)
 		emu_xxh64_carry((const u8 *)d_base, base_bytes, d_jobs, (u32)njobs, d_states, d_digest, d_verdict);
+	return GPUMT_OK;
+}
+
+/* the record decoders over the emulator (tests/emu/emu_api.cpp) */
+void emu_zstd_decompress_batch(const u8 *stream, u64 stream_bytes, const u64 *rec_off, const u32 *rec_len, u32 nrec, u8 *out,
+			       const u64 *out_off, u32 *out_len, u32 *status);
+
+/* gpumt_zstd_decompress_batch_par with its knobs as arguments (cap_mb: 0 = none); stats (may be NULL) receives what the
+ * trace line of the real boundary prints: records, par, blocks, slices, fallback */
+void emu_zstd_decompress_batch_par(const u8 *stream, u64 stream_bytes, const u64 *rec_off, const u32 *rec_len, u32 nrec, u8 *out,
+				   u64 out_bytes, const u64 *out_off, u32 *out_len, u32 *status, u32 *rec_par, u32 min_blocks,
+				   u32 slice_blocks, int par_on, u32 cap_mb, u32 *stats)
+{
+	u32 st5[5] = {nrec, 0, 0, 0, 0};
+	for (u32 i = 0; rec_par && i < nrec; i++)
+		rec_par[i] = 0;
+	if (!par_on) {
+		emu_zstd_decompress_batch(stream, stream_bytes, rec_off, rec_len, nrec, out, out_off, out_len, status);
+		if (stats)
+			memcpy(stats, st5, sizeof st5);
+		return;
+	}
+	std::vector<ZRec> recv(nrec);
+	std::vector<u32> sst(status, status + nrec), ce(nrec, 0xA5A5A5A5u), cv(nrec, 0), rfv(nrec, 0xA5A5A5A5u), rrv(nrec, 0xA5A5A5A5u);
+	ZRec *recs = recv.data();
+	u32 *sstp = sst.data(), *cep = ce.data(), *cvp = cv.data(), *rfp = rfv.data(), *rrp = rrv.data();
+	emu::launch(emu::dim3{(nrec + 255) / 256, 1, 1}, emu::dim3{256, 1, 1}, [=]() {
+		zmt_zstd_rec_count_kernel(stream, stream_bytes, rec_off, rec_len, nrec, out_off, out_len, out_bytes, status,
+					  min_blocks, recs);
+	});
+	ZRecSlice S;
+	/* the scratch the real boundary would ask for: per record, and the largest slice's tables */
+	size_t max_blk = 0, max_run = 0, nslices = 0;
+	for (size_t at = 0; zrec_next_slice(recs, nrec, at, slice_blocks, &S); at = S.b) {
+		max_blk = S.nblk > max_blk ? S.nblk : max_blk;
+		max_run = S.nrun > max_run ? S.nrun : max_run;
+		nslices++;
+	}
+	const size_t need = (size_t)nrec * (sizeof(ZRec) + 20) + max_blk * sizeof(ZBlock) + max_run * (sizeof(ZRun) + 8) +
+			    2 * sizeof(ZCarry);
+	if (!nslices || (cap_mb && need > ((size_t)cap_mb << 20))) {
+		st5[4] = nslices ? 1 : 0;
+		emu_zstd_decompress_batch(stream, stream_bytes, rec_off, rec_len, nrec, out, out_off, out_len, status);
+		if (stats)
+			memcpy(stats, st5, sizeof st5);
+		return;
+	}
+	for (size_t at = 0; zrec_next_slice(recs, nrec, at, slice_blocks, &S); at = S.b) {
+		const u32 n = (u32)(S.b - S.a), nblk = S.nblk, nrun = S.nrun;
+		std::vector<ZBlock> blkv(nblk);
+		std::vector<ZRun> runv(nrun);
+		std::vector<u32> rlv(nrun, 0xA5A5A5A5u), rsv(nrun, 99u);
+		std::vector<u8> cyv(2 * sizeof(ZCarry), 0xA5);
+		ZBlock *blk = blkv.data();
+		ZRun *run = runv.data();
+		u32 *rl = rlv.data(), *rs = rsv.data();
+		const ZRec *sr = recs + S.a;
+		u32 *sf = rfp + S.a, *sn = rrp + S.a;
+		const u64 in_lo = S.in_lo, out_lo = S.out_lo;
+		emu::launch(emu::dim3{1, 1, 1}, emu::dim3{256, 1, 1}, [=]() { zmt_zstd_rec_scan_kernel(sr, n, sf, sn); });
+		emu::launch(emu::dim3{(n + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+			    [=]() { zmt_zstd_rec_table_kernel(stream, sr, n, sf, sn, in_lo, out_lo, nblk, nrun, blk, run); });
+		emu_zstd_decompress_blocks_par(stream + S.in_lo, S.in_hi - S.in_lo, blk, nblk, run, nrun, out + S.out_lo,
+					       S.out_hi - S.out_lo, cyv.data(), rl, rs, nullptr, nullptr, 1);
+		u32 *ol = out_len + S.a, *rp = rec_par ? rec_par + S.a : nullptr, *ss = sstp + S.a, *e = cep + S.a, *v = cvp + S.a;
+		emu::launch(emu::dim3{(n + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+			    [=]() { zmt_zstd_rec_finish_kernel(stream, sr, n, sn, nrun, rl, rs, ol, rp, ss, e, v); });
+		st5[1] += nrun;
+		st5[2] += nblk;
+		st5[3]++;
+	}
+	/* the record decoders judge everything the block stages did not keep (their own checksum pass included) */
+	emu_zstd_decompress_batch(stream, stream_bytes, rec_off, rec_len, nrec, out, out_off, out_len, sstp);
+	emu::launch(emu::dim3{(nrec + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_zstd_rec_merge_kernel(sstp, nrec, status); });
+	emu::launch(emu::dim3{(nrec * 4 + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_xxh64_verify_kernel(out, out_off, out_len, nrec, cep, cvp, status); });
+	if (stats)
+		memcpy(stats, st5, sizeof st5);
+}
+
+static int emu_rec_env(const char *name, int lo, int hi, int dflt)
+{
+	const char *e = getenv(name);
+	if (!e || !*e)
+		return dflt;
+	char *end;
+	const long v = strtol(e, &end, 10);
+	if (*end || v < lo || v > hi) {
+		fprintf(stderr, "gpumt: %s=%s ignored (%d..%d)\n", name, e, lo, hi);
+		return dflt;
+	}
+	return (int)v;
+}
+
+int gpumt_zstd_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				    const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				    const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int s)
+{
+	static_assert(sizeof(ZRec) == 56, "record layout");
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	/* (the environment alone, as the block calls above; read once, by whichever thread comes first: the initialisation of
+	 * a function-local static is synchronised) */
+	struct Knobs {
+		int min_blocks, slice_blocks, trace;
+		Knobs()
+		{
+			const char *e = getenv("GPUMT_TRACE");
+			trace = e && *e ? atoi(e) : 0;
+			slice_blocks = emu_rec_env("GPUMT_ZSTD_REC_SLICE_BLOCKS", 2, 65536, 4096);
+			min_blocks = emu_rec_env("GPUMT_ZSTD_REC_MIN_BLOCKS", 1, 65536, 4);
+		}
+	};
+	static const Knobs knobs;
+	const int min_blocks = knobs.min_blocks, slice_blocks = knobs.slice_blocks, trace = knobs.trace;
+	u32 st5[5];
+	emu_zstd_decompress_batch_par((const u8 *)d_stream, stream_bytes, d_rec_off, d_rec_len, (u32)nrec, (u8 *)d_out, out_bytes,
+				      d_out_off, d_out_len, d_status, d_rec_par, (u32)min_blocks, (u32)slice_blocks, 1, 0, st5);
+	if (trace >= 1)
+		fprintf(stderr, "[gpumt zstd rec] records %u par %u blocks %u slices %u fallback %u\n", st5[0], st5[1], st5[2], st5[3],
+			st5[4]);
 	return GPUMT_OK;
 }
 }

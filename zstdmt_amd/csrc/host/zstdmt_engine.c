@@ -118,7 +118,22 @@ static int zstd_compress_batch(gpumt_ctx *g, const void *d_in, size_t n, size_t 
 #define MT_D_DEFAULT_INPUTSIZE (1024 * 512) /* zstd-mt_decompress.c:125-128 */
 #define MT_D12_CHECK_SIZE_FIELD 0
 #define MT_D12_STATUS_PRESET 1
-#define MT_DECOMPRESS_BATCH gpumt_zstd_decompress_batch
+/* GPUMT_ZSTD_REC_PAR=1 (exactly that) hands the batch to gpumt_zstd_decompress_batch_par, which decodes the records of
+ * several blocks block-parallel: same records, statuses, sizes and bytes; unset or anything else, the call is the one below,
+ * byte for byte.  Read per batch by the launching thread; a weak reference, as for the encoder above */
+extern __typeof__(gpumt_zstd_decompress_batch_par) gpumt_zstd_decompress_batch_par __attribute__((weak));
+static int zstd_decompress_batch(gpumt_ctx *g, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				 const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				 const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, int stream)
+{
+	const char *e = gpumt_zstd_decompress_batch_par ? getenv("GPUMT_ZSTD_REC_PAR") : NULL;
+	if (e && e[0] == '1' && !e[1])
+		return gpumt_zstd_decompress_batch_par(g, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes,
+						       d_out_off, d_out_len, d_status, NULL, stream);
+	return gpumt_zstd_decompress_batch(g, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					   d_out_len, d_status, stream);
+}
+#define MT_DECOMPRESS_BATCH zstd_decompress_batch
 #define MT_FRAME_MAGIC ZSTDCB_MAGICNUMBER_MAX
 #define MT_PLAIN_REQUEST(ctx) ((void)(ctx), (size_t)ZSTD_IN_CHUNK)
 #define MT_PLAIN_PIECE(ctx) ((void)(ctx), (size_t)ZSTD_OUT_CHUNK)
