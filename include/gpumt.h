@@ -186,6 +186,55 @@ int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream
 			       uint32_t *d_out_len, uint32_t *d_status, int stream);
 
 /*
+ * gpumt_lz4_decompress_batch with the records of several linked blocks decoded block-parallel (opt-in; what
+ * GPUMT_LZ4_REC_PAR=1 makes LZ4MT_decompressDCtx call).  Same arguments and slack rule, and for every record the same
+ * status and d_out_len; for every record whose status is GPUMT_ST_OK the same output bytes (the output range of a record
+ * that fails is unspecified, as in the block calls), and nothing outside a record's [d_out_off[i], d_out_off[i] +
+ * d_out_len[i]) is written.  d_rec_par (nrec words, may be NULL) receives per record the number of its blocks whose result
+ * came from the block call on the tables made here and was kept, 0 for every other record.  A return value other than
+ * GPUMT_OK (a launch failed) leaves the batch undefined.
+ * The stages, stream-ordered, none of which waits on another wave (lz4_dec_rec.h; the LZ4 twin of
+ * gpumt_zstd_decompress_batch_par below):
+ *   count   one lane per record checks the 12-byte header and the LZ4F frame header (magic, version, reserved bits, BD,
+ *           content size, dictID, header checksum) and hops from block header to block header to the end mark.  A record is
+ *           eligible when both headers are well formed, the blocks are linked, the stated content size equals d_out_len[i],
+ *           is not 0 and at most 0xFFFE0000, every block lies inside the record with a size of at most the frame's block
+ *           maximum, the end mark is there, exactly the promised 4 checksum bytes (or none) follow it, and the record has
+ *           lz4_rec_min_blocks .. 65536 parts: blocks, or on the seg route max(blocks, ceil(content / lz4_seg_bytes)).
+ *           Block checksums, a dictID and block maxima above 64 KiB are eligible; frames of independent blocks and frames
+ *           without a content size are not.  The stage decides no verdict.
+ *   (host)  one copy of the counts to pinned memory and one hipStreamSynchronize of `stream`: the host cuts the batch into
+ *           slices of consecutive records with at most 4096 eligible records, lz4_rec_slice_blocks blocks (a record of
+ *           more is a slice of its own) and 0xFFFFFFF0 stream bytes.  A slice passes d_stream and d_out offset to its first
+ *           eligible record (rounded down to 256), so the origin plane of the block call is 2 x the slice's output span.
+ *   table   per slice a scan of the block counts, then one lane per eligible record writes its gpumt_lz4_block entries
+ *           (stored flag, block checksum word, blkmax) and one gpumt_lz4_run (low = out_off, out_cap = the content size).
+ *   blocks  gpumt_lz4_decompress_blocks_par, or gpumt_lz4_decompress_blocks_seg with the handle's lz4_seg_bytes, on the
+ *           slice's tables, unchanged: either falls back by its own rules.
+ *   finish  one lane per eligible record keeps it when the run's status is OK and its length is the stated content size.
+ *           A kept record gets d_rec_par, its content checksum words, and a mark in a scratch status word.
+ *   records the record decoders of gpumt_lz4_decompress_batch over the whole batch with those words as their "kept" array:
+ *           a kept record is passed by, every other record is decoded and judged there, so the verdicts are the serial
+ *           call's by construction.  A merge writes GPUMT_ST_OK for the kept records and the XXH32 verify runs once over
+ *           all records.
+ * Internal scratch: areas of its own, which the block calls and the record decoders do not replace -- 76 bytes per record
+ * and, for the largest slice, 32 bytes per block and 40 per eligible record -- next to theirs.  If the device refuses them,
+ * or they exceed lz4_rec_cap_mb, the call is gpumt_lz4_decompress_batch (d_rec_par 0) and that size is not asked for again.
+ * gpumt_set_variant: "lz4_rec_par" 1 = default, 0 = the record decoders alone; "lz4_rec_seg" 0 = blocks_par (default), 1 =
+ * blocks_seg (GPUMT_LZ4_REC_SEG); "lz4_rec_min_blocks" 2..65536 (default 4096, from profiles/lz4_rec_par.txt: records of
+ * 64 KiB blocks decode faster through the record decoders up to 1024 blocks per record, records the record decoders give to
+ * one wave each -- block checksums, a dictID, blocks above 64 KiB -- decode 2 to 8 times faster through this call from 4
+ * blocks on, so set 4 for those; GPUMT_LZ4_REC_MIN_BLOCKS); "lz4_rec_slice_blocks" 2..65536 (default 4096; GPUMT_LZ4_REC_SLICE_BLOCKS); "lz4_rec_cap_mb"
+ * (0 = none).  Values out of range are refused with -1 and change nothing.  With GPUMT_TRACE=1 every call prints
+ * `[gpumt lz4 rec] records N par P blocks B slices S fallback F route seg|par` (P eligible records with B blocks in S calls
+ * of the block stages; F = 1: this stage's own scratch was refused and the record decoders took the whole batch).
+ */
+int gpumt_lz4_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+				   const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
+				   void *d_out, size_t out_bytes, const uint64_t *d_out_off,
+				   uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int stream);
+
+/*
  * Block-level LZ4 decode: what the plain .lz4 path of LZ4MT_decompressDCtx uses in place of one record per frame
  * (replaces the streaming LZ4F_decompress of st_decompress, lib/lz4-mt_decompress.c:391-483).  The caller walks the
  * frame and block headers and passes a table of blocks and a list of runs; one wave decodes a run, its blocks back to

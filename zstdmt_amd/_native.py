@@ -54,6 +54,7 @@ GPUMT_SYMBOLS = {
     "gpumt_lz4_compact": (_i, [_vp, _vp, _sz, _u32p, _sz, _vp, _u64p, _i]),
     "gpumt_lz4_probe_sizes": (_i, [_vp, _vp, _u64p, _u32p, _sz, _u32p, _u64p, _i]),
     "gpumt_lz4_decompress_batch": (_i, [_vp, _vp, _sz, _u64p, _u32p, _sz, _vp, _sz, _u64p, _u32p, _u32p, _i]),
+    "gpumt_lz4_decompress_batch_par": (_i, [_vp, _vp, _sz, _u64p, _u32p, _sz, _vp, _sz, _u64p, _u32p, _u32p, _u32p, _i]),
     "gpumt_lz4_decompress_blocks": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _u32p, _u32p, _u32p, _i]),
     "gpumt_lz4_decompress_blocks_par": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _u32p, _u32p, _u32p, _i]),
     "gpumt_lz4_decompress_blocks_seg": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _u32p, _u32p, _u32p, _u32p, _i]),

@@ -20,6 +20,9 @@ typedef uint64_t u64;
 /* record layout and slice rule of gpumt_zstd_decompress_batch_par */
 #define ZREC_HOST_ONLY
 #include "zstd_dec_rec.h"
+/* ... and of gpumt_lz4_decompress_batch_par */
+#define LREC_HOST_ONLY
+#include "lz4_dec_rec.h"
 
 extern "C" {
 __global__ void zmt_xxh32_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *, const u32 *,
@@ -42,6 +45,8 @@ __global__ void zmt_lz4_enc3_u32_kernel(const u8 *, u64, u32, u32, u32, u8 *, u6
 					unsigned long long *);
 __global__ void zmt_lz4_dec_serial(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *,
 				   u32 *, u32 *, u32 *, u32 *, u32);
+__global__ void zmt_lz4_dec_serial_kept(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *,
+					u32 *, u32 *, u32 *, u32 *, u32, const u32 *);
 /* scratch of gpumt_zstd_decompress_blocks_par (zstd_dec_par.h) */
 struct ZPar {
 	u32 *origin;
@@ -96,6 +101,15 @@ __global__ void zmt_lz4_seg_scan_kernel(const u8 *, u64, const gpumt_lz4_block *
 					u32 *, u32 *, u32 *, Lz4Seg);
 __global__ void zmt_lz4_seg_exec_kernel(const u8 *, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u8 *, Lz4Seg);
 __global__ void zmt_lz4_seg_resolve_kernel(const gpumt_lz4_run *, u32, u32, u8 *, u64, u32 *, u32 *, u32 *, u32 *, Lz4Seg);
+/* the record stage in front of the two (lz4_dec_rec.h) */
+__global__ void zmt_lz4_rec_count_kernel(const u8 *, u64, const u64 *, const u32 *, u32, const u64 *, const u32 *, u64, u32,
+					 u32, LRec *);
+__global__ void zmt_lz4_rec_scan_kernel(const LRec *, u32, u32 *, u32 *);
+__global__ void zmt_lz4_rec_table_kernel(const u8 *, const LRec *, u32, const u32 *, const u32 *, u64, u64, u32, u32,
+					 gpumt_lz4_block *, gpumt_lz4_run *);
+__global__ void zmt_lz4_rec_finish_kernel(const u8 *, const LRec *, u32, const u32 *, u32, const u32 *, const u32 *, u32 *,
+					  u32 *, u32 *, u32 *, u32 *);
+__global__ void zmt_lz4_rec_merge_kernel(const u32 *, u32, u32 *, u32 *);
 __global__ void zmt_lz4_dec_blocks_kernel(const u8 *, u64, const gpumt_lz4_block *, u32, const gpumt_lz4_run *, u32, u8 *,
 					  u64, u32 *, u32 *, u32 *);
 __global__ void zmt_lz4_gather_runs_kernel(const u8 *, u64, const gpumt_lz4_run *, const u32 *, const u64 *, u32, u8 *,
@@ -104,6 +118,8 @@ __global__ void zmt_xxh32_carry_kernel(const u8 *, u64, const gpumt_xxh32_job *,
 __global__ void zmt_dec_nblk_kernel(const u32 *, u32, u32 *);
 __global__ void zmt_dec_frames_kernel(const u8 *, const u64 *, const u32 *, u32, const u32 *,
 				      const u64 *, u64 *, u32 *, u32 *, u32 *, u32 *, u32 *, u32 *);
+__global__ void zmt_dec_frames_kept_kernel(const u8 *, const u64 *, const u32 *, u32, const u32 *,
+					   const u64 *, u64 *, u32 *, u32 *, u32 *, u32 *, u32 *, u32 *, const u32 *);
 __global__ void zmt_dec_parse4_kernel(const u8 *, u64, const u64 *, const u32 *, const u64 *, u16 *, u32 *, u32 *);
 #define C3_DECL(NAME)                                                                                              \
 	__global__ void NAME(const u8 *, u64, u32, u32, u8 *, const u64 *, const u32 *, const u64 *, const u64 *,  \
@@ -222,6 +238,18 @@ struct gpumt_ctx {
 	int lblk_seg;     /* 1 = plain .lz4 blocks in segments side by side (gpumt_lz4_decompress_blocks_seg); 0 = one wave per run */
 	int lseg_bytes;   /* the segment of that call: a power of two, 256 .. 4 MiB */
 	size_t lblk_seg_refused; /* the same for that call's scratch */
+	int lrec_par;     /* 1 = multi-block lz4-mt records through the block calls (gpumt_lz4_decompress_batch_par); 0 = the record decoders alone */
+	int lrec_seg;     /* 0 = gpumt_lz4_decompress_blocks_par decodes the slices, 1 = gpumt_lz4_decompress_blocks_seg */
+	int lrec_min_blocks;   /* records of fewer parts stay with the record decoders */
+	int lrec_slice_blocks; /* blocks per call of the block stages */
+	int lrec_cap_mb;  /* 0 = none; else that stage's own scratch above this many MiB counts as refused (the tests' way to the fallback) */
+	size_t lrec_refused; /* the smallest such scratch the device has refused (0 = none yet): not asked for again */
+	void *lrec_area[GPUMT_NSTREAMS]; /* that stage's own device scratch: the block calls and the record decoders replace scratch[1] */
+	size_t lrec_bytes[GPUMT_NSTREAMS];
+	void *lrec_tab[GPUMT_NSTREAMS];  /* ... and its tables per slice, sized once the counts are known */
+	size_t lrec_tab_bytes[GPUMT_NSTREAMS];
+	void *lrec_pin[GPUMT_NSTREAMS]; /* pinned copy of the per-record counts, for the host to cut slices */
+	size_t lrec_pin_bytes[GPUMT_NSTREAMS];
 	int sdec_variant; /* snappy decoder: 0 = element by element, 1 = 64 elements per batch (snappy.hip) */
 	int bdec_variant; /* brotli decoder: 0 = by batch size, 1 = the general kernel only, 2 = dec4 (four records per wave) + general for what it hands over */
 	int bdec_waves;   /* resident waves of the persistent brotli decoder kernel (whole device) */
@@ -427,6 +455,25 @@ int gpumt_open(int device, gpumt_ctx **out)
 			else
 				fprintf(stderr, "gpumt: GPUMT_LZ4_BLOCK_SEG=%s ignored (0 or 1)\n", e);
 		}
+		/* gpumt_lz4_decompress_batch_par: GPUMT_LZ4_REC_SEG (0 or 1), GPUMT_LZ4_REC_MIN_BLOCKS and
+		 * GPUMT_LZ4_REC_SLICE_BLOCKS (2..65536) */
+		h->lrec_par = 1;
+		h->lrec_seg = 0;
+		h->lrec_min_blocks = 4096; /* profiles/lz4_rec_par.txt */
+		h->lrec_slice_blocks = 4096;
+		for (int k = 0; k < 3; k++) {
+			const char *name = k == 0 ? "GPUMT_LZ4_REC_SEG" : k == 1 ? "GPUMT_LZ4_REC_MIN_BLOCKS" : "GPUMT_LZ4_REC_SLICE_BLOCKS";
+			const long lo = k ? 2 : 0, hi = k ? 65536 : 1;
+			e = getenv(name);
+			if (e && *e) {
+				char *end;
+				const long v = strtol(e, &end, 10);
+				if (*end || v < lo || v > hi)
+					fprintf(stderr, "gpumt: %s=%s ignored (%ld..%ld)\n", name, e, lo, hi);
+				else
+					*(k == 0 ? &h->lrec_seg : k == 1 ? &h->lrec_min_blocks : &h->lrec_slice_blocks) = (int)v;
+			}
+		}
 		e = getenv("GPUMT_TRACE");
 		h->trace = e && *e ? atoi(e) : 0;
 		/* GPUMT_BROTLI_DEC: 0 = the batch size chooses (default), 1 = the general kernel, 2 = dec4 first */
@@ -459,6 +506,12 @@ void gpumt_close(gpumt_ctx *h)
 			dev_free(h, h->zrec_tab[i]);
 		if (h->zrec_pin[i])
 			(void)hipHostFree(h->zrec_pin[i]);
+		if (h->lrec_area[i])
+			dev_free(h, h->lrec_area[i]);
+		if (h->lrec_tab[i])
+			dev_free(h, h->lrec_tab[i]);
+		if (h->lrec_pin[i])
+			(void)hipHostFree(h->lrec_pin[i]);
 	}
 	for (int i = 0; i < NTIMERS; i++) {
 		(void)hipEventDestroy(h->t0[i]);
@@ -1043,15 +1096,16 @@ int gpumt_lz4_probe_sizes(gpumt_ctx *h, const void *d_stream, const uint64_t *d_
 	return GPUMT_OK;
 }
 
-int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
-			       const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
-			       void *d_out, size_t out_bytes, const uint64_t *d_out_off,
-			       uint32_t *d_out_len, uint32_t *d_status, int s)
+/* The record decoders.  gpumt_lz4_decompress_batch passes no kept array and no checksum words: it launches the kernels it
+ * always launched, the words lie in the scratch and the verify pass follows.  gpumt_lz4_decompress_batch_par passes its
+ * scratch status words as `kept` (ST_REC_KEPT = the block stages decoded the record) and checksum words of its own: the frame
+ * and the serial kernel are then their _kept entries -- the frame kernel leaves such a record's block-table slots empty and
+ * writes that word to d_status, so parse4, copy3 and the serial kernel pass it by -- and the verify pass is the caller's. */
+static int lz4_decompress_records(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				  const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				  const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, const u32 *kept, u32 *x_ce,
+				  u32 *x_cv, int s)
 {
-	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
-		return GPUMT_E_ARG;
-	if (use(h))
-		return GPUMT_E_HIP;
 	const u32 n = (u32)nrec;
 	const unsigned g256 = (unsigned)((nrec + 255) / 256);
 	/* scratch carve-up (all offsets 16-byte aligned) */
@@ -1081,7 +1135,7 @@ int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream
 	if (want_scratch(h, 1, s, split ? off : nrec * 8 + 32))
 		return GPUMT_E_HIP;
 	u8 *sc = (u8 *)h->scratch[1][s];
-	u32 *ce = (u32 *)(sc + ce_o), *cv = (u32 *)(sc + cv_o);
+	u32 *ce = x_ce ? x_ce : (u32 *)(sc + ce_o), *cv = x_ce ? x_cv : (u32 *)(sc + cv_o);
 	PROF0(11);
 	if (split) {
 		u32 *est = (u32 *)(sc + est_o), *rnb = (u32 *)(sc + rnb_o), *rfl = (u32 *)(sc + rfl_o);
@@ -1091,9 +1145,14 @@ int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream
 		PROF0(13);
 		hipLaunchKernelGGL(zmt_dec_nblk_kernel, dim3(g256), dim3(256), 0, h->st[s], d_out_len, n, est);
 		hipLaunchKernelGGL(zmt_scan_kernel, dim3(1), dim3(1024), 0, h->st[s], (const u32 *)est, n, blk0);
-		hipLaunchKernelGGL(zmt_dec_frames_kernel, dim3(g256), dim3(256), 0, h->st[s],
-				   (const u8 *)d_stream, d_rec_off, d_rec_len, n, d_out_len,
-				   (const u64 *)blk0, bco, bcs, rnb, rfl, d_status, ce, cv);
+		if (kept)
+			hipLaunchKernelGGL(zmt_dec_frames_kept_kernel, dim3(g256), dim3(256), 0, h->st[s],
+					   (const u8 *)d_stream, d_rec_off, d_rec_len, n, d_out_len,
+					   (const u64 *)blk0, bco, bcs, rnb, rfl, d_status, ce, cv, kept);
+		else
+			hipLaunchKernelGGL(zmt_dec_frames_kernel, dim3(g256), dim3(256), 0, h->st[s],
+					   (const u8 *)d_stream, d_rec_off, d_rec_len, n, d_out_len,
+					   (const u64 *)blk0, bco, bcs, rnb, rfl, d_status, ce, cv);
 		PROF1(13);
 		const int ring = h->lz4_ring < 12 ? 12 : h->lz4_ring > 14 ? 14 : h->lz4_ring;
 		PROF0(14);
@@ -1133,22 +1192,46 @@ int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream
 		}
 		PROF1(15);
 		/* records the fast path does not cover (block size > 64 KiB, odd block counts) */
-		hipLaunchKernelGGL(zmt_lz4_dec_serial, dim3(n), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+		if (kept)
+			hipLaunchKernelGGL(zmt_lz4_dec_serial_kept, dim3(n), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+					   d_rec_off, d_rec_len, n, (u8 *)d_out, d_out_off, d_out_len, d_status, ce,
+					   cv, 100u, kept);
+		else
+			hipLaunchKernelGGL(zmt_lz4_dec_serial, dim3(n), dim3(64), 0, h->st[s], (const u8 *)d_stream,
+					   d_rec_off, d_rec_len, n, (u8 *)d_out, d_out_off, d_out_len, d_status, ce,
+					   cv, 100u);
+	} else if (kept) {
+		hipLaunchKernelGGL(zmt_lz4_dec_serial_kept, dim3(n), dim3(64), 0, h->st[s], (const u8 *)d_stream,
 				   d_rec_off, d_rec_len, n, (u8 *)d_out, d_out_off, d_out_len, d_status, ce,
-				   cv, 100u);
+				   cv, 0xFFFFFFFFu, kept);
 	} else {
 		hipLaunchKernelGGL(zmt_lz4_dec_serial, dim3(n), dim3(64), 0, h->st[s], (const u8 *)d_stream,
 				   d_rec_off, d_rec_len, n, (u8 *)d_out, d_out_off, d_out_len, d_status, ce,
 				   cv, 0xFFFFFFFFu);
 	}
 	PROF1(11);
-	PROF0(12);
-	hipLaunchKernelGGL(zmt_xxh32_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), dim3(256), 0,
-			   h->st[s], (const u8 *)d_out, d_out_off, d_out_len, n, (u32 *)NULL,
-			   (const u32 *)ce, (const u32 *)cv, d_status);
-	PROF1(12);
+	if (!x_ce) {
+		PROF0(12);
+		hipLaunchKernelGGL(zmt_xxh32_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), dim3(256), 0,
+				   h->st[s], (const u8 *)d_out, d_out_off, d_out_len, n, (u32 *)NULL,
+				   (const u32 *)ce, (const u32 *)cv, d_status);
+		PROF1(12);
+	}
 	CK(hipGetLastError());
 	return GPUMT_OK;
+}
+
+int gpumt_lz4_decompress_batch(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
+			       const uint64_t *d_rec_off, const uint32_t *d_rec_len, size_t nrec,
+			       void *d_out, size_t out_bytes, const uint64_t *d_out_off,
+			       uint32_t *d_out_len, uint32_t *d_status, int s)
+{
+	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	return lz4_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off, d_out_len,
+				      d_status, NULL, NULL, NULL, s);
 }
 
 int gpumt_lz4_decompress_blocks(gpumt_ctx *h, const void *d_stream, size_t stream_bytes,
@@ -1971,6 +2054,144 @@ int gpumt_zstd_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t s
 	return GPUMT_OK;
 }
 
+/* gpumt_zstd_decompress_batch_par's structure with the LZ4 block calls behind it (lz4_dec_rec.h) */
+int gpumt_lz4_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				   const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				   const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int s)
+{
+	static_assert(sizeof(LRec) == 56, "record layout");
+	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	const hipStream_t st = h->st[s];
+	const int seg = h->lrec_seg;
+	const char *route = seg ? "seg" : "par";
+	if (d_rec_par)
+		CK(hipMemsetAsync(d_rec_par, 0, nrec * 4, st));
+	if (!h->lrec_par) {
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt lz4 rec] records %zu par 0 blocks 0 slices 0 fallback 0 route %s\n", nrec, route);
+		return lz4_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					      d_out_len, d_status, NULL, NULL, NULL, s);
+	}
+	/* the stage's own areas, which the block calls and the record decoders do not replace.  Per record: the counts and five
+	 * words (scratch status = the record decoders' kept array, checksum expected / valid, first block, run).  Per slice,
+	 * sized once the counts are known: the block table with length and segment count per block, and the run table with
+	 * length and status per run */
+	const size_t rec_bytes = (nrec * sizeof(LRec) + 255) & ~(size_t)255, word_bytes = (nrec * 4 + 255) & ~(size_t)255;
+	const size_t need_a = rec_bytes + 5 * word_bytes;
+	const size_t cap = h->lrec_cap_mb ? (size_t)h->lrec_cap_mb << 20 : ~(size_t)0;
+	int par = !(h->lrec_refused && need_a >= h->lrec_refused);
+	if (par && need_a > cap) {
+		h->lrec_refused = need_a;
+		par = 0;
+	}
+	if (par && zrec_want(h, &h->lrec_area[s], &h->lrec_bytes[s], need_a, st)) {
+		h->lrec_refused = need_a;
+		par = 0;
+	}
+	if (par && rec_bytes > h->lrec_pin_bytes[s]) {
+		/* (the copy that read the old area was waited for by the call that queued it) */
+		void *p = NULL;
+		if (hipHostMalloc(&p, rec_bytes, hipHostMallocDefault) != hipSuccess || !p) {
+			(void)hipGetLastError();
+			h->lrec_refused = need_a;
+			par = 0;
+		} else {
+			if (h->lrec_pin[s])
+				(void)hipHostFree(h->lrec_pin[s]);
+			h->lrec_pin[s] = p;
+			h->lrec_pin_bytes[s] = rec_bytes;
+		}
+	}
+	if (!par) {
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt lz4 rec] records %zu par 0 blocks 0 slices 0 fallback 1 route %s\n", nrec, route);
+		return lz4_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					      d_out_len, d_status, NULL, NULL, NULL, s);
+	}
+	u8 *area = (u8 *)h->lrec_area[s];
+	LRec *recs = (LRec *)area;
+	u32 *sstatus = (u32 *)(area + rec_bytes), *chk_e = (u32 *)((u8 *)sstatus + word_bytes);
+	u32 *chk_v = (u32 *)((u8 *)chk_e + word_bytes), *rfirst = (u32 *)((u8 *)chk_v + word_bytes);
+	u32 *rrun = (u32 *)((u8 *)rfirst + word_bytes);
+	const u8 *stream = (const u8 *)d_stream;
+	const dim3 per_rec((unsigned)((nrec + 255) / 256)), tpb(256);
+	hipLaunchKernelGGL(zmt_lz4_rec_count_kernel, per_rec, tpb, 0, st, stream, (u64)stream_bytes, d_rec_off, d_rec_len, (u32)nrec,
+			   d_out_off, (const u32 *)d_out_len, (u64)out_bytes, (u32)h->lrec_min_blocks, seg ? (u32)h->lseg_bytes : 0u,
+			   recs);
+	/* one round trip: the host sizes the tables and the launches of the block stages from the counts */
+	const LRec *hrec = (const LRec *)h->lrec_pin[s];
+	CK(hipMemcpyAsync(h->lrec_pin[s], recs, nrec * sizeof(LRec), hipMemcpyDeviceToHost, st));
+	CK(hipStreamSynchronize(st));
+	const u32 SB = (u32)h->lrec_slice_blocks;
+	size_t npar = 0, nblocks = 0, nslices = 0, max_blk = 0, max_run = 0;
+	LRecSlice S;
+	for (size_t at = 0; lrec_next_slice(hrec, nrec, at, SB, &S); at = S.b) {
+		npar += S.nrun;
+		nblocks += S.nblk;
+		nslices++;
+		max_blk = S.nblk > max_blk ? S.nblk : max_blk;
+		max_run = S.nrun > max_run ? S.nrun : max_run;
+	}
+	const size_t blk_bytes = (max_blk * (sizeof(gpumt_lz4_block) + 8) + 255) & ~(size_t)255;
+	const size_t run_bytes = (max_run * (sizeof(gpumt_lz4_run) + 8) + 255) & ~(size_t)255;
+	const size_t need_b = blk_bytes + run_bytes, need = need_a + need_b;
+	if (nslices && ((h->lrec_refused && need >= h->lrec_refused) || need > cap ||
+			zrec_want(h, &h->lrec_tab[s], &h->lrec_tab_bytes[s], need_b, st))) {
+		h->lrec_refused = need;
+		par = 0;
+	}
+	if (!par || !nslices) {
+		/* nothing for the block stages (or no room for their tables): the record decoders alone */
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt lz4 rec] records %zu par 0 blocks 0 slices 0 fallback %d route %s\n", nrec, par ? 0 : 1,
+				route);
+		return lz4_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					      d_out_len, d_status, NULL, NULL, NULL, s);
+	}
+	gpumt_lz4_block *blocks = (gpumt_lz4_block *)h->lrec_tab[s];
+	u32 *blk_len = (u32 *)(blocks + max_blk), *blk_seg = blk_len + max_blk;
+	gpumt_lz4_run *runs = (gpumt_lz4_run *)((u8 *)blocks + blk_bytes);
+	u32 *run_len = (u32 *)(runs + max_run), *run_st = run_len + max_run;
+	CK(hipMemsetAsync(sstatus, 0, nrec * 4, st));
+	CK(hipMemsetAsync(chk_v, 0, nrec * 4, st));
+	/* the slices first, the record pass after them: the block calls replace scratch[1][s], which the record pass carves up */
+	for (size_t at = 0; lrec_next_slice(hrec, nrec, at, SB, &S); at = S.b) {
+		const u32 n = (u32)(S.b - S.a);
+		hipLaunchKernelGGL(zmt_lz4_rec_scan_kernel, dim3(1), tpb, 0, st, (const LRec *)(recs + S.a), n, rfirst + S.a, rrun + S.a);
+		hipLaunchKernelGGL(zmt_lz4_rec_table_kernel, dim3((n + 255) / 256), tpb, 0, st, stream, (const LRec *)(recs + S.a), n,
+				   (const u32 *)(rfirst + S.a), (const u32 *)(rrun + S.a), S.in_lo, S.out_lo, S.nblk, S.nrun, blocks,
+				   runs);
+		/* the existing call, with d_stream and d_out at the slice: its origin plane is 2 x the slice's output span */
+		const int rc = seg ? gpumt_lz4_decompress_blocks_seg(h, stream + S.in_lo, (size_t)(S.in_hi - S.in_lo), blocks, S.nblk,
+								     runs, S.nrun, (u8 *)d_out + S.out_lo,
+								     (size_t)(S.out_hi - S.out_lo), blk_len, run_len, run_st, blk_seg, s)
+				   : gpumt_lz4_decompress_blocks_par(h, stream + S.in_lo, (size_t)(S.in_hi - S.in_lo), blocks, S.nblk,
+								     runs, S.nrun, (u8 *)d_out + S.out_lo,
+								     (size_t)(S.out_hi - S.out_lo), blk_len, run_len, run_st, s);
+		if (rc != GPUMT_OK)
+			return rc;
+		hipLaunchKernelGGL(zmt_lz4_rec_finish_kernel, dim3((n + 255) / 256), tpb, 0, st, stream, (const LRec *)(recs + S.a), n,
+				   (const u32 *)(rrun + S.a), S.nrun, (const u32 *)run_len, (const u32 *)run_st, d_out_len + S.a,
+				   d_rec_par ? d_rec_par + S.a : (u32 *)NULL, sstatus + S.a, chk_e + S.a, chk_v + S.a);
+	}
+	if (h->trace >= 1)
+		fprintf(stderr, "[gpumt lz4 rec] records %zu par %zu blocks %zu slices %zu fallback 0 route %s\n", nrec, npar, nblocks,
+			nslices, route);
+	/* everything the block stages did not keep is decoded and judged by the record decoders */
+	const int rc = lz4_decompress_records(h, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					      d_out_len, d_status, (const u32 *)sstatus, chk_e, chk_v, s);
+	if (rc != GPUMT_OK)
+		return rc;
+	hipLaunchKernelGGL(zmt_lz4_rec_merge_kernel, per_rec, tpb, 0, st, (const u32 *)sstatus, (u32)nrec, d_status, d_rec_par);
+	hipLaunchKernelGGL(zmt_xxh32_kernel, dim3((unsigned)((nrec * 4 + 255) / 256)), tpb, 0, st, (const u8 *)d_out, d_out_off,
+			   (const u32 *)d_out_len, (u32)nrec, (u32 *)NULL, (const u32 *)chk_e, (const u32 *)chk_v, d_status);
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
+
 int gpumt_xxh64_carry(gpumt_ctx *h, const void *d_base, size_t base_bytes, const gpumt_xxh32_job *d_jobs, size_t njobs,
 		      uint32_t *d_states, uint32_t *d_digest, uint32_t *d_verdict, int s)
 {
@@ -2371,6 +2592,32 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 			return -1;
 		prev = h->lseg_bytes;
 		h->lseg_bytes = variant;
+	} else if (!strcmp(what, "lz4_rec_par")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->lrec_par;
+		h->lrec_par = variant;
+	} else if (!strcmp(what, "lz4_rec_seg")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->lrec_seg;
+		h->lrec_seg = variant;
+	} else if (!strcmp(what, "lz4_rec_min_blocks")) {
+		if (variant < 2 || variant > 65536)
+			return -1;
+		prev = h->lrec_min_blocks;
+		h->lrec_min_blocks = variant;
+	} else if (!strcmp(what, "lz4_rec_slice_blocks")) {
+		if (variant < 2 || variant > 65536)
+			return -1;
+		prev = h->lrec_slice_blocks;
+		h->lrec_slice_blocks = variant;
+	} else if (!strcmp(what, "lz4_rec_cap_mb")) {
+		if (variant < 0)
+			return -1;
+		prev = h->lrec_cap_mb;
+		h->lrec_cap_mb = variant;
+		h->lrec_refused = 0; /* (a new cap: ask again) */
 	} else if (!strcmp(what, "snappy_dec")) {
 		prev = h->sdec_variant;
 		h->sdec_variant = variant;

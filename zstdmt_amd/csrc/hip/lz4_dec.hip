@@ -116,12 +116,13 @@ static __device__ u32 wave_xxh32(const u8 *p, u32 len, int lane)
 	return wv_readlane(h, 0);
 }
 
-extern "C" __global__ void __launch_bounds__(64)
-zmt_lz4_dec_serial(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
-		   const u32 *__restrict__ rec_len, u32 nrec, u8 *out_base,
-		   const u64 *__restrict__ out_off, u32 *__restrict__ out_len,
-		   u32 *__restrict__ status, u32 *__restrict__ chk_expect,
-		   u32 *__restrict__ chk_valid, u32 only_status)
+static __device__ __forceinline__ void
+lz4_dec_serial_body(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
+		    const u32 *__restrict__ rec_len, u32 nrec, u8 *out_base,
+		    const u64 *__restrict__ out_off, u32 *__restrict__ out_len,
+		    u32 *__restrict__ status, u32 *__restrict__ chk_expect,
+		    u32 *__restrict__ chk_valid, u32 only_status,
+		    const u32 *__restrict__ kept) /* NULL, or per record ST_REC_KEPT = pass it by */
 {
 	const u32 rec = blockIdx.x;
 	const int lane = wv_lane();
@@ -130,6 +131,11 @@ zmt_lz4_dec_serial(const u8 *__restrict__ stream, const u64 *__restrict__ rec_of
 	/* clean-up pass of the split decoder: only records it flagged for this kernel */
 	if (only_status != 0xFFFFFFFFu && wv_readfirst(status[rec]) != only_status)
 		return;
+	if (kept && wv_readfirst(kept[rec]) == ST_REC_KEPT) {
+		if (lane == 0)
+			status[rec] = ST_REC_KEPT; /* (as zmt_dec_frames_kept_kernel: the caller's merge reads it as "passed by") */
+		return;
+	}
 	const u8 *r = stream + rec_off[rec];
 	const u32 rlen = rec_len[rec];
 	u8 *out = out_base + out_off[rec];
@@ -214,6 +220,29 @@ zmt_lz4_dec_serial(const u8 *__restrict__ stream, const u64 *__restrict__ rec_of
 done:
 	if (lane == 0)
 		status[rec] = st;
+}
+
+extern "C" __global__ void __launch_bounds__(64)
+zmt_lz4_dec_serial(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
+		   const u32 *__restrict__ rec_len, u32 nrec, u8 *out_base,
+		   const u64 *__restrict__ out_off, u32 *__restrict__ out_len,
+		   u32 *__restrict__ status, u32 *__restrict__ chk_expect,
+		   u32 *__restrict__ chk_valid, u32 only_status)
+{
+	lz4_dec_serial_body(stream, rec_off, rec_len, nrec, out_base, out_off, out_len, status, chk_expect, chk_valid, only_status,
+			    nullptr);
+}
+
+/* the same kernel for gpumt_lz4_decompress_batch_par's record pass: records whose kept word is ST_REC_KEPT are passed by */
+extern "C" __global__ void __launch_bounds__(64)
+zmt_lz4_dec_serial_kept(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
+			const u32 *__restrict__ rec_len, u32 nrec, u8 *out_base,
+			const u64 *__restrict__ out_off, u32 *__restrict__ out_len,
+			u32 *__restrict__ status, u32 *__restrict__ chk_expect,
+			u32 *__restrict__ chk_valid, u32 only_status, const u32 *__restrict__ kept)
+{
+	lz4_dec_serial_body(stream, rec_off, rec_len, nrec, out_base, out_off, out_len, status, chk_expect, chk_valid, only_status,
+			    kept);
 }
 
 /*
@@ -339,6 +368,7 @@ zmt_lz4_gather_runs_kernel(const u8 *__restrict__ out_base, u64 out_bytes, const
 
 #include "lz4_dec_par.h"
 #include "lz4_dec_seg.h"
+#include "lz4_dec_rec.h"
 
 #ifdef ZMT_EMU
 /*
@@ -507,6 +537,180 @@ int gpumt_lz4_pack_runs(gpumt_ctx *h, const void *d_out, size_t out_bytes, const
 	if ((const u8 *)d_packed < (const u8 *)d_out + out_bytes && (const u8 *)d_out < (const u8 *)d_packed + packed_bytes)
 		return GPUMT_E_ARG;
 	emu_lz4_pack_runs((const u8 *)d_out, out_bytes, d_runs, d_run_len, (u32)nrun, (u8 *)d_packed, packed_bytes, d_pack_off);
+	return GPUMT_OK;
+}
+
+/* the record decoders over the emulator: emu_lz4_decompress_batch (tests/emu/emu_api.cpp) is gpumt_lz4_decompress_batch;
+ * emu_lz4_records_kept is the record pass of gpumt_lz4_decompress_batch_par, the same launches with the kernels that take
+ * the kept array, the caller's checksum words and no verify pass (variant: 1 = the wave-per-record kernel alone) */
+void zmt_xxh32_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *, const u32 *, const u32 *, u32 *);
+void zmt_dec_nblk_kernel(const u32 *, u32, u32 *);
+void zmt_dec_frames_kept_kernel(const u8 *, const u64 *, const u32 *, u32, const u32 *, const u64 *, u64 *, u32 *, u32 *, u32 *,
+				u32 *, u32 *, u32 *, const u32 *);
+void zmt_dec_parse4_kernel(const u8 *, u64, const u64 *, const u32 *, const u64 *, u16 *, u32 *, u32 *);
+void zmt_dec_copy3_w4_kernel(const u8 *, u64, u32, u32, u8 *, const u64 *, const u32 *, const u64 *, const u64 *, const u32 *,
+			     const u32 *, const u32 *, const u16 *, const u32 *, const u32 *, u32 *);
+void emu_lz4_decompress_batch(int variant, const u8 *stream, u64 stream_bytes, const u64 *rec_off, const u32 *rec_len,
+			      u32 nrec, u8 *out, u64 out_bytes, const u64 *out_off, u32 *out_len, u32 *status);
+
+static void emu_lz4_records_kept(int variant, const u8 *stream, u64 stream_bytes, const u64 *rec_off, const u32 *rec_len,
+				 u32 nrec, u8 *out, u64 out_bytes, const u64 *out_off, u32 *out_len, u32 *status,
+				 const u32 *kept, u32 *cep, u32 *cvp)
+{
+	if (variant == 1) {
+		emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+			zmt_lz4_dec_serial_kept(stream, rec_off, rec_len, nrec, out, out_off, out_len, status, cep, cvp, 0xFFFFFFFFu, kept);
+		});
+		return;
+	}
+	const size_t nblk_max = out_bytes / 65536 + nrec + 1;
+	const size_t ntok_max = stream_bytes / 3 + 128 * nblk_max + 256;
+	/* scratch starts as garbage, like device memory */
+	std::vector<u32> est(nrec, 0xA5A5A5A5u), rnb(nrec, 0xA5A5A5A5u), rfl(nrec, 0xA5A5A5A5u), bcs(nblk_max, 0x00A5A5A5u),
+		bnt(nblk_max, 0xA5A5A5A5u), bol(nblk_max, 0xA5A5A5A5u);
+	std::vector<u64> blk0(nrec + 1, 0xA5A5A5A5A5A5A5A5ull), bco(nblk_max, 0x00A5A5A5A5A5A5A5ull);
+	std::vector<u16> tok(ntok_max, 0xA5A5);
+	u32 *estp = est.data(), *rnbp = rnb.data(), *rflp = rfl.data(), *bcsp = bcs.data(), *bntp = bnt.data(), *bolp = bol.data();
+	u64 *blk0p = blk0.data(), *bcop = bco.data();
+	u16 *tokp = tok.data();
+	emu::launch(emu::dim3{(nrec + 255) / 256, 1, 1}, emu::dim3{256, 1, 1}, [=]() { zmt_dec_nblk_kernel(out_len, nrec, estp); });
+	emu::launch(emu::dim3{1, 1, 1}, emu::dim3{1024, 1, 1}, [=]() { zmt_scan_kernel(estp, nrec, blk0p); });
+	emu::launch(emu::dim3{(nrec + 255) / 256, 1, 1}, emu::dim3{256, 1, 1}, [=]() {
+		zmt_dec_frames_kept_kernel(stream, rec_off, rec_len, nrec, out_len, blk0p, bcop, bcsp, rnbp, rflp, status, cep, cvp, kept);
+	});
+	emu::launch(emu::dim3{(u32)((nblk_max + 63) / 64), 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_dec_parse4_kernel(stream, stream_bytes, bcop, bcsp, blk0p + nrec, tokp, bntp, bolp);
+	});
+	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_dec_copy3_w4_kernel(stream, stream_bytes, 0, nrec, out, out_off, out_len, blk0p, bcop, bcsp, rnbp, rflp, tokp, bntp, bolp,
+					status);
+	});
+	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		zmt_lz4_dec_serial_kept(stream, rec_off, rec_len, nrec, out, out_off, out_len, status, cep, cvp, 100u, kept);
+	});
+}
+
+/* gpumt_lz4_decompress_batch_par with its knobs as arguments (variant: the record decoders' pipeline, as
+ * emu_lz4_decompress_batch; seg_on: the seg route with seg_bytes; cap_mb: 0 = none); stats (may be NULL) receives what the
+ * trace line of the real boundary prints: records, par, blocks, slices, fallback */
+void emu_lz4_decompress_batch_par(int variant, const u8 *stream, u64 stream_bytes, const u64 *rec_off, const u32 *rec_len,
+				  u32 nrec, u8 *out, u64 out_bytes, const u64 *out_off, u32 *out_len, u32 *status, u32 *rec_par,
+				  u32 min_blocks, u32 slice_blocks, int par_on, int seg_on, u32 seg_bytes, u32 cap_mb, u32 *stats)
+{
+	u32 st5[5] = {nrec, 0, 0, 0, 0};
+	for (u32 i = 0; rec_par && i < nrec; i++)
+		rec_par[i] = 0;
+	if (!par_on) {
+		emu_lz4_decompress_batch(variant, stream, stream_bytes, rec_off, rec_len, nrec, out, out_bytes, out_off, out_len, status);
+		if (stats)
+			memcpy(stats, st5, sizeof st5);
+		return;
+	}
+	std::vector<LRec> recv(nrec);
+	std::vector<u32> sst(nrec, 0), ce(nrec, 0xA5A5A5A5u), cv(nrec, 0), rfv(nrec, 0xA5A5A5A5u), rrv(nrec, 0xA5A5A5A5u);
+	LRec *recs = recv.data();
+	u32 *sstp = sst.data(), *cep = ce.data(), *cvp = cv.data(), *rfp = rfv.data(), *rrp = rrv.data();
+	const u32 count_seg = seg_on ? seg_bytes : 0;
+	emu::launch(emu::dim3{(nrec + 255) / 256, 1, 1}, emu::dim3{256, 1, 1}, [=]() {
+		zmt_lz4_rec_count_kernel(stream, stream_bytes, rec_off, rec_len, nrec, out_off, out_len, out_bytes, min_blocks,
+					 count_seg, recs);
+	});
+	LRecSlice S;
+	/* the scratch the real boundary would ask for: per record, and the largest slice's tables */
+	size_t max_blk = 0, max_run = 0, nslices = 0;
+	for (size_t at = 0; lrec_next_slice(recs, nrec, at, slice_blocks, &S); at = S.b) {
+		max_blk = S.nblk > max_blk ? S.nblk : max_blk;
+		max_run = S.nrun > max_run ? S.nrun : max_run;
+		nslices++;
+	}
+	const size_t need = (size_t)nrec * (sizeof(LRec) + 20) + max_blk * (sizeof(Lz4Block) + 8) + max_run * (sizeof(Lz4Run) + 8);
+	if (!nslices || (cap_mb && need > ((size_t)cap_mb << 20))) {
+		st5[4] = nslices ? 1 : 0;
+		emu_lz4_decompress_batch(variant, stream, stream_bytes, rec_off, rec_len, nrec, out, out_bytes, out_off, out_len, status);
+		if (stats)
+			memcpy(stats, st5, sizeof st5);
+		return;
+	}
+	for (size_t at = 0; lrec_next_slice(recs, nrec, at, slice_blocks, &S); at = S.b) {
+		const u32 n = (u32)(S.b - S.a), nblk = S.nblk, nrun = S.nrun;
+		std::vector<Lz4Block> blkv(nblk);
+		std::vector<Lz4Run> runv(nrun);
+		std::vector<u32> blv(nblk, 0xA5A5A5A5u), bsv(nblk, 0xA5A5A5A5u), rlv(nrun, 0xA5A5A5A5u), rsv(nrun, 99u);
+		Lz4Block *blk = blkv.data();
+		Lz4Run *run = runv.data();
+		u32 *rl = rlv.data(), *rs = rsv.data();
+		const LRec *sr = recs + S.a;
+		u32 *sf = rfp + S.a, *sn = rrp + S.a;
+		const u64 in_lo = S.in_lo, out_lo = S.out_lo;
+		emu::launch(emu::dim3{1, 1, 1}, emu::dim3{256, 1, 1}, [=]() { zmt_lz4_rec_scan_kernel(sr, n, sf, sn); });
+		emu::launch(emu::dim3{(n + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+			    [=]() { zmt_lz4_rec_table_kernel(stream, sr, n, sf, sn, in_lo, out_lo, nblk, nrun, blk, run); });
+		if (seg_on)
+			emu_lz4_decompress_blocks_seg(stream + S.in_lo, S.in_hi - S.in_lo, blk, nblk, run, nrun, out + S.out_lo,
+						      S.out_hi - S.out_lo, blv.data(), rl, rs, bsv.data(), 1, seg_bytes);
+		else
+			emu_lz4_decompress_blocks_par(stream + S.in_lo, S.in_hi - S.in_lo, blk, nblk, run, nrun, out + S.out_lo,
+						      S.out_hi - S.out_lo, blv.data(), rl, rs, 1);
+		u32 *ol = out_len + S.a, *rp = rec_par ? rec_par + S.a : nullptr, *ss = sstp + S.a, *e = cep + S.a, *v = cvp + S.a;
+		emu::launch(emu::dim3{(n + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+			    [=]() { zmt_lz4_rec_finish_kernel(stream, sr, n, sn, nrun, rl, rs, ol, rp, ss, e, v); });
+		st5[1] += nrun;
+		st5[2] += nblk;
+		st5[3]++;
+	}
+	/* the record decoders judge everything the block stages did not keep */
+	emu_lz4_records_kept(variant, stream, stream_bytes, rec_off, rec_len, nrec, out, out_bytes, out_off, out_len, status, sstp, cep,
+			     cvp);
+	emu::launch(emu::dim3{(nrec + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_lz4_rec_merge_kernel(sstp, nrec, status, rec_par); });
+	emu::launch(emu::dim3{(nrec * 4 + 255) / 256, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_xxh32_kernel(out, out_off, out_len, nrec, nullptr, cep, cvp, status); });
+	if (stats)
+		memcpy(stats, st5, sizeof st5);
+}
+
+static int emu_lrec_env(const char *name, int lo, int hi, int dflt)
+{
+	const char *e = getenv(name);
+	if (!e || !*e)
+		return dflt;
+	char *end;
+	const long v = strtol(e, &end, 10);
+	if (*end || v < lo || v > hi) {
+		fprintf(stderr, "gpumt: %s=%s ignored (%d..%d)\n", name, e, lo, hi);
+		return dflt;
+	}
+	return (int)v;
+}
+
+int gpumt_lz4_decompress_batch_par(gpumt_ctx *h, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				   const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				   const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int s)
+{
+	static_assert(sizeof(LRec) == 56, "record layout");
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	/* (the environment alone, as the block calls above; read once, by whichever thread comes first: the initialisation of
+	 * a function-local static is synchronised) */
+	struct Knobs {
+		int min_blocks, slice_blocks, seg, trace;
+		Knobs()
+		{
+			const char *e = getenv("GPUMT_TRACE");
+			trace = e && *e ? atoi(e) : 0;
+			slice_blocks = emu_lrec_env("GPUMT_LZ4_REC_SLICE_BLOCKS", 2, 65536, 4096);
+			min_blocks = emu_lrec_env("GPUMT_LZ4_REC_MIN_BLOCKS", 2, 65536, 4096);
+			seg = emu_lrec_env("GPUMT_LZ4_REC_SEG", 0, 1, 0);
+		}
+	};
+	static const Knobs knobs;
+	u32 st5[5];
+	emu_lz4_decompress_batch_par(0, (const u8 *)d_stream, stream_bytes, d_rec_off, d_rec_len, (u32)nrec, (u8 *)d_out, out_bytes,
+				     d_out_off, d_out_len, d_status, d_rec_par, (u32)knobs.min_blocks, (u32)knobs.slice_blocks, 1,
+				     knobs.seg, 65536u, 0, st5);
+	if (knobs.trace >= 1)
+		fprintf(stderr, "[gpumt lz4 rec] records %u par %u blocks %u slices %u fallback %u route %s\n", st5[0], st5[1], st5[2],
+			st5[3], st5[4], knobs.seg ? "seg" : "par");
 	return GPUMT_OK;
 }
 }

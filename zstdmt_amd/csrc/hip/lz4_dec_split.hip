@@ -38,14 +38,15 @@ zmt_dec_nblk_kernel(const u32 *__restrict__ out_len, u32 nrec, u32 *__restrict__
 }
 
 /* ------------------------------------------------------------------------------------- K1 */
-extern "C" __global__ void __launch_bounds__(256)
-zmt_dec_frames_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
-		      const u32 *__restrict__ rec_len, u32 nrec, const u32 *__restrict__ out_len,
-		      const u64 *__restrict__ blk0, /* exclusive scan of ceil(out_len/64K) */
-		      u64 *__restrict__ blk_coff, u32 *__restrict__ blk_csize,
-		      u32 *__restrict__ rec_nblk, u32 *__restrict__ rec_flags,
-		      u32 *__restrict__ status, u32 *__restrict__ chk_expect,
-		      u32 *__restrict__ chk_valid)
+static __device__ __forceinline__ void
+dec_frames_body(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
+		const u32 *__restrict__ rec_len, u32 nrec, const u32 *__restrict__ out_len,
+		const u64 *__restrict__ blk0, /* exclusive scan of ceil(out_len/64K) */
+		u64 *__restrict__ blk_coff, u32 *__restrict__ blk_csize,
+		u32 *__restrict__ rec_nblk, u32 *__restrict__ rec_flags,
+		u32 *__restrict__ status, u32 *__restrict__ chk_expect,
+		u32 *__restrict__ chk_valid,
+		const u32 *__restrict__ kept) /* NULL, or per record ST_REC_KEPT = pass it by */
 {
 	const u32 rec = blockIdx.x * 256 + threadIdx.x;
 	if (rec >= nrec)
@@ -59,14 +60,19 @@ zmt_dec_frames_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec
 	u32 st = ST_OK, nb = 0, ip = 0, flen = 0, hdr, flg, bd;
 	u32 has_csize = 0, has_ccheck = 0, indep = 0;
 
-	chk_valid[rec] = 0;
-	chk_expect[rec] = 0;
 	rec_nblk[rec] = 0;
 	rec_flags[rec] = 0;
 	/* every slot of this record in the block table must be defined for the parse kernel, also
 	 * when the record is rejected below */
 	for (u32 i = 0; i < nb_max; i++)
 		blk_csize[b0 + i] = BLK_EMPTY;
+	if (kept && kept[rec] == ST_REC_KEPT) {
+		/* decoded already: nothing to parse or copy, and the checksum words are the caller's */
+		status[rec] = ST_REC_KEPT;
+		return;
+	}
+	chk_valid[rec] = 0;
+	chk_expect[rec] = 0;
 	if (rlen < 12 || ld32u(r) != ZMT_SKIP_MAGIC || ld32u(r + 4) != 4 || ld32u(r + 8) != rlen - 12) {
 		status[rec] = ST_BAD_RECORD;
 		return;
@@ -159,4 +165,31 @@ zmt_dec_frames_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec
 	rec_nblk[rec] = nb;
 	rec_flags[rec] = indep;
 	status[rec] = st;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+zmt_dec_frames_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
+		      const u32 *__restrict__ rec_len, u32 nrec, const u32 *__restrict__ out_len,
+		      const u64 *__restrict__ blk0, u64 *__restrict__ blk_coff, u32 *__restrict__ blk_csize,
+		      u32 *__restrict__ rec_nblk, u32 *__restrict__ rec_flags,
+		      u32 *__restrict__ status, u32 *__restrict__ chk_expect,
+		      u32 *__restrict__ chk_valid)
+{
+	dec_frames_body(stream, rec_off, rec_len, nrec, out_len, blk0, blk_coff, blk_csize, rec_nblk, rec_flags, status, chk_expect,
+			chk_valid, nullptr);
+}
+
+/* the same kernel for gpumt_lz4_decompress_batch_par's record pass: a record whose kept word is ST_REC_KEPT was decoded by
+ * the block stages -- its block-table slots stay BLK_EMPTY, its checksum words are not touched, and d_status gets
+ * ST_REC_KEPT, so parse4, copy3 and the serial kernel have nothing to do for it */
+extern "C" __global__ void __launch_bounds__(256)
+zmt_dec_frames_kept_kernel(const u8 *__restrict__ stream, const u64 *__restrict__ rec_off,
+			   const u32 *__restrict__ rec_len, u32 nrec, const u32 *__restrict__ out_len,
+			   const u64 *__restrict__ blk0, u64 *__restrict__ blk_coff, u32 *__restrict__ blk_csize,
+			   u32 *__restrict__ rec_nblk, u32 *__restrict__ rec_flags,
+			   u32 *__restrict__ status, u32 *__restrict__ chk_expect,
+			   u32 *__restrict__ chk_valid, const u32 *__restrict__ kept)
+{
+	dec_frames_body(stream, rec_off, rec_len, nrec, out_len, blk0, blk_coff, blk_csize, rec_nblk, rec_flags, status, chk_expect,
+			chk_valid, kept);
 }

@@ -18,6 +18,12 @@ static __device__ __forceinline__ void wave_mem_fence()
 #endif
 }
 
+/* internal, in a "kept" word array only: gpumt_lz4_decompress_batch_par's block stages decoded the record (lz4_dec_rec.h),
+ * and the record decoders pass it by -- its bytes, its length and its checksum words are not touched */
+#ifndef ST_REC_KEPT
+#define ST_REC_KEPT 102u
+#endif
+
 struct FrameInfo {
 	u32 hdr;       /* header bytes */
 	u32 blkmax;

@@ -72,7 +72,22 @@ const char *LZ4MT_getErrorString(size_t code)
 #define MT_D_DEFAULT_INPUTSIZE (1024 + 1024 * 4) /* sic, lz4-mt_decompress.c:115 */
 #define MT_D12_CHECK_SIZE_FIELD 1
 #define MT_D12_STATUS_PRESET 0
-#define MT_DECOMPRESS_BATCH gpumt_lz4_decompress_batch
+/* GPUMT_LZ4_REC_PAR=1 (exactly that) hands the batch to gpumt_lz4_decompress_batch_par, which decodes the records of
+ * several linked blocks block-parallel: same records, statuses, sizes and bytes; unset or anything else, the call is the
+ * one below, byte for byte.  Read per batch by the launching thread; a weak reference, as in zstdmt_engine.c */
+extern __typeof__(gpumt_lz4_decompress_batch_par) gpumt_lz4_decompress_batch_par __attribute__((weak));
+static int lz4_decompress_batch(gpumt_ctx *g, const void *d_stream, size_t stream_bytes, const uint64_t *d_rec_off,
+				const uint32_t *d_rec_len, size_t nrec, void *d_out, size_t out_bytes,
+				const uint64_t *d_out_off, uint32_t *d_out_len, uint32_t *d_status, int stream)
+{
+	const char *e = gpumt_lz4_decompress_batch_par ? getenv("GPUMT_LZ4_REC_PAR") : NULL;
+	if (e && e[0] == '1' && !e[1])
+		return gpumt_lz4_decompress_batch_par(g, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes,
+						      d_out_off, d_out_len, d_status, NULL, stream);
+	return gpumt_lz4_decompress_batch(g, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes, d_out_off,
+					  d_out_len, d_status, stream);
+}
+#define MT_DECOMPRESS_BATCH lz4_decompress_batch
 #define MT_FRAME_MAGIC LZ4FMT_MAGICNUMBER
 #define MT_PLAIN_REQUEST(ctx) ((size_t)(ctx)->inputsize) /* inputsize requests, lz4-mt_decompress.c:462-476 */
 #define MT_PLAIN_PIECE(ctx) ((ctx)->inputsize < 65536 ? (size_t)65536 : (size_t)(ctx)->inputsize)

@@ -193,6 +193,41 @@ class Engine:
                                                    int(out_bytes), d_out_off.ptr, d_out_len.ptr,
                                                    d_status.ptr, stream), "lz4_decompress_batch")
 
+    def lz4_decompress_par(self, d_stream, stream_bytes, d_rec_off, d_rec_len, nrec, d_out, out_bytes,
+                           d_out_off, d_out_len, d_status, d_rec_par=None, stream=0):
+        """gpumt_lz4_decompress_batch_par: lz4_decompress with the records of several linked blocks decoded block-parallel;
+        d_rec_par (nrec words, may be None) receives per record the blocks that route decoded and kept"""
+        self._ck(self.L.gpumt_lz4_decompress_batch_par(self.h, d_stream.ptr, int(stream_bytes), d_rec_off.ptr,
+                                                       d_rec_len.ptr, nrec, d_out.ptr, int(out_bytes), d_out_off.ptr,
+                                                       d_out_len.ptr, d_status.ptr,
+                                                       d_rec_par.ptr if d_rec_par is not None else None, stream),
+                 "lz4_decompress_batch_par")
+
+    def lz4_decompress_par_bytes(self, stream: bytes, rec_off, rec_len):
+        """decompress_bytes for lz4-mt records through lz4_decompress_par -> (content bytes, status[n], rec_par[n])"""
+        nrec = len(rec_len)
+        d_stream = self.upload(stream)
+        d_ro = self.upload(np.asarray(rec_off, np.uint64)[:nrec].copy())
+        d_rl = self.upload(np.asarray(rec_len, np.uint32).copy())
+        d_ol, d_oo, d_st, d_rp = self.alloc(nrec * 4), self.alloc((nrec + 1) * 8), self.alloc(nrec * 4), self.alloc(nrec * 4)
+        try:
+            self.lz4_probe(d_stream, d_ro, d_rl, nrec, d_ol, d_oo)
+            total = int(self.download(d_oo, (nrec + 1) * 8, np.uint64)[nrec])
+            d_out = self.alloc(total + 64)
+            try:
+                lib().gpumt_memset(self.h, d_out.ptr, 0xCC, total + 64, 0)
+                self.lz4_decompress_par(d_stream, len(stream), d_ro, d_rl, nrec, d_out, total, d_oo, d_ol, d_st, d_rp)
+                status = self.download(d_st, nrec * 4, np.uint32)
+                rec_par = self.download(d_rp, nrec * 4, np.uint32)
+                raw = self.download(d_out, total + 64)
+                assert (raw[total:] == 0xCC).all(), "decoder wrote past the end of its output"
+            finally:
+                d_out.free()
+        finally:
+            for b in (d_stream, d_ro, d_rl, d_ol, d_oo, d_st, d_rp):
+                b.free()
+        return raw[:total].tobytes(), status, rec_par
+
     def lz4_decompress_blocks(self, stream: bytes, blocks, runs, out_bytes, history=b"", pack=False, blk_fill=0,
                               call="gpumt_lz4_decompress_blocks"):
         """gpumt_lz4_decompress_blocks over host bytes: `blocks` / `runs` are LZ4_BLOCK / LZ4_RUN arrays, `history` is
