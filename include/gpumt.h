@@ -424,6 +424,32 @@ int gpumt_zstd_win_depth(int level);
 int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
 				  size_t slot_stride, uint32_t *d_rec_len, int level, int stream);
 
+/*
+ * The chain plane of both window encoders on its own, and its segment-parallel build (opt-in).
+ * gpumt_win_chain_plane writes the n words of the plane of d_in cut into chunks -- word p = the nearest earlier position of
+ * p's chunk (chunk-relative) whose next 6 bytes hash alike, or 0xFFFFFFFF -- to d_plane; n <= 1 GiB, chunk <= 2^27, and d_in
+ * has the encoders' readable slack behind it.  seg_log 0: one wave builds a chunk, 64 positions per step in order, as both _win
+ * calls do by default.  seg_log 12..24: a chunk is cut into segments of 1 << seg_log positions, persistent waves chain each
+ * segment over a head table of its own, a second launch carries the head tables forward through the chunk's segments and a
+ * third gives every position without a predecessor in its segment the one the earlier segments hold: the same plane, word
+ * for word, whatever the input (where no chunk has more than one segment the first kernel runs).  Anything else is
+ * GPUMT_E_ARG.  The head tables take gpumt_win_chain_par_scratch(n, chunk, seg_log) bytes of internal scratch -- per segment
+ * 4 << min(17, max(12, log2(min(chunk, n)) - 3)) bytes; 0 where the segment build does not run -- and this call never builds
+ * the plane another way than asked: head tables the device or "win_chain_cap_mb" refuses are GPUMT_E_NOMEM.
+ * gpumt_set_variant(h, "win_chain_par", k) makes gpumt_zstd_compress_batch_win and gpumt_brotli_compress_batch_win build
+ * their plane in segments: 0 = off (the default), 1 = on at seg_log 20 (profiles/win_chain_par.txt), 12..24 = on at that seg_log, anything else is
+ * rejected (-1); GPUMT_WIN_CHAIN_PAR in the environment holds the same values when the context is opened (unset, empty and
+ * any other text = off).  Both calls then ask for their scratch with the head tables of the largest slice behind it first;
+ * refused -- by the device, or above "win_chain_cap_mb" MiB (0 = none), the tests' way there -- they build the plane with one
+ * wave per chunk, remember the refused size (not asked for again; a new cap asks again) and go on as without the variant.
+ * The records are byte for byte those without the variant in every case.  With GPUMT_TRACE=1 a second line follows
+ * theirs: `[gpumt win chain] segments N seg_log L heads B serial S` (the segments of the largest slice, the head-table
+ * bytes asked for, S = 1 where one wave per chunk built the plane).
+ */
+size_t gpumt_win_chain_par_scratch(size_t n, size_t chunk, int seg_log);
+int gpumt_win_chain_plane(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, uint32_t *d_plane, int seg_log,
+			  int stream);
+
 int gpumt_zstd_probe_sizes(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off,
 			   const uint32_t *d_rec_len, size_t nrec, uint32_t *d_out_len,
 			   uint64_t *d_out_off, uint32_t *d_status, int stream);

@@ -66,6 +66,8 @@ GPUMT_SYMBOLS = {
     "gpumt_zstd_level_tier": (_i, [_i]),
     "gpumt_zstd_win_depth": (_i, [_i]),
     "gpumt_zstd_compress_batch_win": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i, _i]),
+    "gpumt_win_chain_par_scratch": (_sz, [_sz, _sz, _i]),
+    "gpumt_win_chain_plane": (_i, [_vp, _vp, _sz, _sz, _u32p, _i, _i]),
     "gpumt_zstd_probe_sizes": (_i, [_vp, _vp, _u64p, _u32p, _sz, _u32p, _u64p, _u32p, _i]),
     "gpumt_zstd_decompress_batch": (_i, [_vp, _vp, _sz, _u64p, _u32p, _sz, _vp, _sz, _u64p, _u32p, _u32p, _i]),
     "gpumt_zstd_decompress_batch_par": (_i, [_vp, _vp, _sz, _u64p, _u32p, _sz, _vp, _sz, _u64p, _u32p, _u32p, _u32p, _i]),

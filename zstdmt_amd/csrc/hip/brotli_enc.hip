@@ -947,16 +947,30 @@ zmt_brotli_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__re
 #include "../../../include/gpumt.h"
 extern "C" {
 void emu_brotli_compress_batch_level(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level);
-void emu_zstd_win_chain(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 grid); /* zstd_enc.hip: the one chain kernel */
 size_t emu_zstd_slot_stride(size_t chunk);
 
 int gpumt_brotli_win_depth(int level) { return level < 9 ? 0 : level == 9 ? 16 : level == 10 ? 32 : 64; }
+
+/* zstd_enc.hip: the plane by the serial kernel (seg_log 0) or in segments, and the two variables that choose */
+void emu_win_chain_build(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 grid, u32 seg_log, u64 chain_cap, u64 info[3]);
+void emu_win_chain_env(u32 *seg_log, u64 *cap);
+
+static u32 emu_brotli_compress_batch_win_chain(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid,
+					       int level, u32 depth, u64 cap, u32 seg_log, u64 chain_cap, u64 info[3]);
 
 /* depth: 0 = by level.  cap: the scratch the "device" grants, 0 = any -- a request above it is refused and the call
  * encodes with the table encoder of the quality, as below quality 9.  Returns the depth the window encoder ran with, 0
  * where the table encoder ran */
 u32 emu_brotli_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level,
 				  u32 depth, u64 cap)
+{
+	u64 info[3];
+	return emu_brotli_compress_batch_win_chain(in, n, chunk, slots, stride, rec_len, grid, level, depth, cap, 0, 0, info);
+}
+
+/* the same with the plane built by emu_win_chain_build(seg_log, chain_cap) */
+static u32 emu_brotli_compress_batch_win_chain(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid,
+					       int level, u32 depth, u64 cap, u32 seg_log, u64 chain_cap, u64 info[3])
 {
 	const u32 nrec = n ? (u32)((n + chunk - 1) / chunk) : 1;
 	const u32 bpr = (chunk + BE_BLOCK - 1) / BE_BLOCK;
@@ -974,7 +988,7 @@ u32 emu_brotli_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64
 	std::vector<u8> seq((size_t)grid * BE_WSCRATCH, 0xA5);
 	u32 *bl = blk_len.data(), *pl = plane.data();
 	u8 *sq = seq.data();
-	emu_zstd_win_chain(in, n, chunk, pl, grid);
+	emu_win_chain_build(in, n, chunk, pl, grid, seg_log, chain_cap, info);
 	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1},
 		    [=]() { zmt_brotli_enc_win_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq, pl, depth); });
 	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{256, 1, 1},
@@ -983,7 +997,8 @@ u32 emu_brotli_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64
 }
 
 /* (the emulated boundary keeps no variants: GPUMT_BROTLI_WIN_DEPTH and GPUMT_BROTLI_WIN_CAP -- bytes -- stand in for
- * gpumt_set_variant's "brotli_win_depth" and "brotli_win_cap_mb") */
+ * gpumt_set_variant's "brotli_win_depth" and "brotli_win_cap_mb", GPUMT_WIN_CHAIN_PAR and GPUMT_WIN_CHAIN_CAP -- bytes -- for
+ * "win_chain_par" and "win_chain_cap_mb") */
 int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
 				    uint32_t *d_rec_len, int level, int s)
 {
@@ -995,11 +1010,17 @@ int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, si
 	const u64 cap = c && *c ? strtoull(c, 0, 10) : 0;
 	if (dv < 0 || dv > 256)
 		return GPUMT_E_ARG;
-	const u32 ran = emu_brotli_compress_batch_win((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3, level,
-						      (u32)dv, cap);
+	u32 seg_log;
+	u64 chain_cap, info[3];
+	emu_win_chain_env(&seg_log, &chain_cap);
+	const u32 ran = emu_brotli_compress_batch_win_chain((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3,
+							    level, (u32)dv, cap, seg_log, chain_cap, info);
 	if (t && atoi(t) >= 1 && level >= 9)
 		fprintf(stderr, "[gpumt brotli win] records %zu depth %u plane %zu fallback %d\n", n ? (n + chunk - 1) / chunk : (size_t)1, ran,
 			ran ? (size_t)4 * n : (size_t)0, ran ? 0 : 1);
+	if (t && atoi(t) >= 1 && ran && seg_log)
+		fprintf(stderr, "[gpumt win chain] segments %zu seg_log %u heads %zu serial %d\n", (size_t)info[0], seg_log, (size_t)info[1],
+			(int)info[2]);
 	return GPUMT_OK;
 }
 }

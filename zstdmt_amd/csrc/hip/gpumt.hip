@@ -175,6 +175,9 @@ __global__ void zmt_zstd_enc_t2_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64
 __global__ void zmt_zstd_enc_t3_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *);
 __global__ void zmt_zstd_enc_kernel_prof(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *, unsigned long long *);
 __global__ void zmt_zstd_win_chain_kernel(const u8 *, u64, u32, u32, u32 *, u32 *);
+__global__ void zmt_win_chain_seg_kernel(const u8 *, u64, u32, u32, u32, u32, u32, u32 *, u32 *);
+__global__ void zmt_win_chain_carry_kernel(u64, u32, u32, u32, u32, u32, u32 *);
+__global__ void zmt_win_chain_patch_kernel(const u8 *, u64, u32, u32, u32, u32, u32 *, const u32 *);
 __global__ void zmt_zstd_enc_win_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *, const u32 *, u32);
 __global__ void zmt_zstd_assemble_kernel(u64, u32, u32, u32, u8 *, u64, const u32 *, u32 *);
 __global__ void zmt_zstd_probe_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *, u32 *);
@@ -214,6 +217,10 @@ struct gpumt_ctx {
 	int bwin_depth;
 	int bwin_cap_mb;
 	size_t bwin_refused;
+	int wchain_par;   /* the chain plane of both: 0 = one wave per chunk, 1 = in segments of the default size, 12..24 = of 1 << that many positions */
+	int wchain_cap_mb; /* 0 = none; else head tables of the segment build above this many MiB count as refused (the tests' way to the fallback) */
+	size_t wchain_refused; /* the smallest head tables the device has refused (0 = none yet): not asked for again */
+	int wchain_waves; /* resident waves of the segment kernel (whole device) */
 	int trace;        /* GPUMT_TRACE */
 	int hc_waves;     /* developer: grid of the LZ4HC encoder (0 = GPUMT_LZ4HC_WAVES) */
 	int zdec_variant; /* 0 = small-table kernel, then general; 1 = general only */
@@ -473,6 +480,15 @@ int gpumt_open(int device, gpumt_ctx **out)
 				else
 					*(k == 0 ? &h->lrec_seg : k == 1 ? &h->lrec_min_blocks : &h->lrec_slice_blocks) = (int)v;
 			}
+		}
+		/* GPUMT_WIN_CHAIN_PAR: the window encoders' chain plane in segments (gpumt_set_variant "win_chain_par": 1 or
+		 * 12..24); unset, empty and any other text = off */
+		e = getenv("GPUMT_WIN_CHAIN_PAR");
+		if (e && *e) {
+			char *end;
+			const long v = strtol(e, &end, 10);
+			if (!*end && (v == 1 || (v >= 12 && v <= 24)))
+				h->wchain_par = (int)v;
 		}
 		e = getenv("GPUMT_TRACE");
 		h->trace = e && *e ? atoi(e) : 0;
@@ -1511,8 +1527,130 @@ int gpumt_zstd_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, si
 
 /* ---- the whole chunk as the match window (zstd_enc_win.h) ---- */
 #define ZW_HLOG_MAX 17
+#define ZW_HLOG_MIN 12
 #define ZW_MAXDIST (1u << 27)
 #define ZW_SLICE ((size_t)1 << 30) /* input bytes per launch slice: the plane stays within 4 GiB */
+
+/* ---- its chain plane, for the brotli encoder's window as well: one wave per chunk (zmt_zstd_win_chain_kernel) or, with
+ * "win_chain_par", in segments (enc_win_chain_par.h) ---- */
+#define GPUMT_WIN_CHAIN_SEG_DEFAULT 20 /* the lowest median at level 10 and 8 MiB chunks: profiles/win_chain_par.txt */
+
+static u32 zw_hlog_host(size_t clen) /* zw_hlog of zstd_enc_win.h */
+{
+	const int l = 63 - __builtin_clzll((unsigned long long)clen | 1ull) - 3;
+	return (u32)(l > ZW_HLOG_MAX ? ZW_HLOG_MAX : l < ZW_HLOG_MIN ? ZW_HLOG_MIN : l);
+}
+
+size_t gpumt_win_chain_par_scratch(size_t n, size_t chunk, int seg_log)
+{
+	if (!n || !chunk || seg_log < 12 || seg_log > 24)
+		return 0;
+	const size_t cl = n < chunk ? n : chunk, spc = (cl + ((size_t)1 << seg_log) - 1) >> seg_log;
+	if (spc <= 1)
+		return 0; /* no chunk has more than one segment: the serial kernel builds the plane */
+	return ((n + chunk - 1) / chunk * spc * 4) << zw_hlog_host(cl);
+}
+
+static int wchain_seg_log(const gpumt_ctx *h) { return h->wchain_par == 1 ? GPUMT_WIN_CHAIN_SEG_DEFAULT : h->wchain_par; }
+
+/* scratch[0][s] grown to `need` bytes, asked for before the area the stream has is let go: 1 = it holds them, 0 = the
+ * device refused and the old area stays, < 0 = an error */
+static int win_scratch_grow(gpumt_ctx *h, size_t need, int s)
+{
+	if (need <= h->scratch_bytes[0][s])
+		return 1;
+	void *p = dev_alloc(h, need);
+	if (!p) {
+		(void)hipGetLastError(); /* (a refused allocation is no error of the call) */
+		return 0;
+	}
+	if (h->scratch[0][s]) {
+		if (hipStreamSynchronize(h->st[s]) != hipSuccess) {
+			dev_free(h, p);
+			return GPUMT_E_HIP;
+		}
+		dev_free(h, h->scratch[0][s]);
+	}
+	h->scratch[0][s] = p;
+	h->scratch_bytes[0][s] = need;
+	return 1;
+}
+
+/* the _win calls with "win_chain_par" on ask for their scratch and `pheads` bytes of head tables behind it, `total`
+ * together, first: 1 = granted, 0 = refused -- by "win_chain_cap_mb", by the call's own cap (own_cap_mb), by the device, or
+ * because the device refused that much before -- and the serial kernel builds the plane; < 0 = an error */
+static int win_chain_par_ask(gpumt_ctx *h, size_t total, size_t pheads, int own_cap_mb, int s)
+{
+	if (h->wchain_refused && pheads >= h->wchain_refused)
+		return 0;
+	if (h->wchain_cap_mb && pheads > ((size_t)h->wchain_cap_mb << 20)) {
+		h->wchain_refused = pheads;
+		return 0;
+	}
+	if (own_cap_mb && total > ((size_t)own_cap_mb << 20))
+		return 0;
+	const int r = win_scratch_grow(h, total, s);
+	if (r == 0)
+		h->wchain_refused = pheads;
+	return r;
+}
+
+/* the plane of one slice (nr records, ni bytes) on stream s.  heads = a table of 4 << ZW_HLOG_MAX bytes per wave of the
+ * serial kernel's grid cg; pheads = gpumt_win_chain_par_scratch(ni, chunk, seg_log) bytes or NULL.  With pheads and a chunk of
+ * more than one segment: the three launches of enc_win_chain_par.h; else the serial kernel, as before */
+static int win_chain_launch(gpumt_ctx *h, const u8 *in, size_t ni, size_t chunk, size_t nr, u32 *plane, u32 *heads, unsigned cg,
+			    u32 *pheads, int seg_log, int s)
+{
+	if (!pheads || !gpumt_win_chain_par_scratch(ni, chunk, seg_log)) {
+		hipLaunchKernelGGL(zmt_zstd_win_chain_kernel, dim3(cg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nr, plane,
+				   heads);
+		return GPUMT_OK;
+	}
+	if (!h->wchain_waves) {
+		int per_cu = 0;
+		CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, zmt_win_chain_seg_kernel, 64, 0));
+		h->wchain_waves = (per_cu > 0 ? per_cu : 4) * (h->num_cus > 0 ? h->num_cus : 256);
+	}
+	const size_t cl = ni < chunk ? ni : chunk, spc = (cl + ((size_t)1 << seg_log) - 1) >> seg_log, nseg = nr * spc;
+	const u32 hslog = zw_hlog_host(cl);
+	const unsigned sg = (unsigned)(nseg < (size_t)h->wchain_waves ? nseg : (size_t)h->wchain_waves);
+	hipLaunchKernelGGL(zmt_win_chain_seg_kernel, dim3(sg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)seg_log,
+			   (u32)spc, (u32)nseg, hslog, plane, pheads);
+	hipLaunchKernelGGL(zmt_win_chain_carry_kernel, dim3((unsigned)((nr << hslog) / 256)), dim3(256), 0, h->st[s], (u64)ni,
+			   (u32)chunk, (u32)seg_log, (u32)spc, (u32)nr, hslog, pheads);
+	hipLaunchKernelGGL(zmt_win_chain_patch_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, h->st[s], in, (u64)ni,
+			   (u32)chunk, (u32)seg_log, (u32)spc, hslog, plane, (const u32 *)pheads);
+	return GPUMT_OK;
+}
+
+int gpumt_win_chain_plane(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, uint32_t *d_plane, int seg_log, int s)
+{
+	if (!h || !STREAM_OK(s) || chunk == 0 || chunk > ZW_MAXDIST || n > ZW_SLICE || (seg_log != 0 && (seg_log < 12 || seg_log > 24)) ||
+	    (n && (!d_in || !d_plane)))
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	if (!n)
+		return GPUMT_OK;
+	const size_t nrec = gpumt_lz4_record_count(n, chunk);
+	const size_t cwaves = (size_t)4 * (h->num_cus > 0 ? h->num_cus : 256), cgrid = nrec < cwaves ? nrec : cwaves;
+	const size_t o_pheads = cgrid * 4 << ZW_HLOG_MAX, pheads = gpumt_win_chain_par_scratch(n, chunk, seg_log);
+	const size_t need = (o_pheads + pheads + 0xFFFFF) & ~(size_t)0xFFFFF;
+	/* this call never builds the plane another way than asked: refused head tables are an error */
+	if ((pheads && h->wchain_cap_mb && pheads > ((size_t)h->wchain_cap_mb << 20)) || !win_scratch_grow(h, need, s)) {
+		snprintf(h->err, sizeof h->err, "chain plane: %zu bytes of head tables refused", pheads ? pheads : o_pheads);
+		return GPUMT_E_NOMEM;
+	}
+	if (need > h->scratch_bytes[0][s])
+		return GPUMT_E_HIP; /* (win_scratch_grow: the stream did not synchronise) */
+	u32 *heads = (u32 *)h->scratch[0][s];
+	const int rc = win_chain_launch(h, (const u8 *)d_in, n, chunk, nrec, d_plane, heads, (unsigned)cgrid,
+					pheads ? (u32 *)((u8 *)heads + o_pheads) : NULL, seg_log, s);
+	if (rc)
+		return rc;
+	CK(hipGetLastError());
+	return GPUMT_OK;
+}
 
 int gpumt_zstd_win_depth(int level) { return level < 10 ? 0 : level <= 12 ? 8 : level <= 15 ? 16 : level <= 18 ? 32 : 64; }
 
@@ -1550,6 +1688,13 @@ int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size
 		h->zwin_refused = need;
 		win = 0;
 	}
+	/* "win_chain_par": the plane + the head tables of the segment build are asked for first; refused, the serial kernel builds
+	 * the plane and the rest of the call is as without the variant */
+	const int seg_log = wchain_seg_log(h);
+	const size_t pheads = win && seg_log ? gpumt_win_chain_par_scratch(slice_in, chunk, seg_log) : 0;
+	int par = 0;
+	if (pheads && (par = win_chain_par_ask(h, (need + pheads + 0xFFFFF) & ~(size_t)0xFFFFF, pheads, h->zwin_cap_mb, s)) < 0)
+		return GPUMT_E_HIP;
 	if (win && need > h->scratch_bytes[0][s]) {
 		/* ask before letting go of the area the stream has: a refusal must leave the table encoder its scratch */
 		void *p = dev_alloc(h, need);
@@ -1572,6 +1717,10 @@ int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size
 	if (h->trace >= 1)
 		fprintf(stderr, "[gpumt zstd win] records %zu depth %u plane %zu fallback %d\n", nrec, win ? depth : 0u,
 			win ? (size_t)4 * slice_in : (size_t)0, win ? 0 : 1);
+	if (h->trace >= 1 && win && seg_log)
+		fprintf(stderr, "[gpumt win chain] segments %zu seg_log %d heads %zu serial %d\n",
+			pheads ? slice_rec * (((slice_in < chunk ? slice_in : chunk) + ((size_t)1 << seg_log) - 1) >> seg_log) : slice_rec,
+			seg_log, pheads, par ? 0 : 1);
 	if (!win)
 		return gpumt_zstd_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, s);
 	u32 *blk_len = (u32 *)h->scratch[0][s];
@@ -1584,8 +1733,10 @@ int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size
 		const unsigned eg = (unsigned)(nb < egrid ? nb : egrid), cg = (unsigned)(nr < cgrid ? nr : cgrid);
 		const u8 *in = (const u8 *)d_in + i0;
 		u8 *slots = (u8 *)d_slots + r0 * slot_stride;
-		hipLaunchKernelGGL(zmt_zstd_win_chain_kernel, dim3(cg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nr, plane,
-				   heads);
+		const int rc = win_chain_launch(h, in, ni, chunk, nr, plane, heads, cg, par ? (u32 *)((u8 *)h->scratch[0][s] + need) : NULL,
+						seg_log, s);
+		if (rc)
+			return rc;
 		hipLaunchKernelGGL(zmt_zstd_enc_win_kernel, dim3(eg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nb, bpr, slots,
 				   (u64)slot_stride, blk_len, seqbuf, (const u32 *)plane, depth);
 		hipLaunchKernelGGL(zmt_zstd_assemble_kernel, dim3((unsigned)nr), dim3(256), 0, h->st[s], (u64)ni, (u32)chunk, (u32)nr,
@@ -2307,6 +2458,13 @@ int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, si
 		h->bwin_refused = need;
 		win = 0;
 	}
+	/* "win_chain_par": the plane + the head tables of the segment build are asked for first; refused, the serial kernel builds
+	 * the plane and the rest of the call is as without the variant */
+	const int seg_log = wchain_seg_log(h);
+	const size_t pheads = win && seg_log ? gpumt_win_chain_par_scratch(slice_in, chunk, seg_log) : 0;
+	int par = 0;
+	if (pheads && (par = win_chain_par_ask(h, (need + pheads + 0xFFFFF) & ~(size_t)0xFFFFF, pheads, h->bwin_cap_mb, s)) < 0)
+		return GPUMT_E_HIP;
 	if (win && need > h->scratch_bytes[0][s]) {
 		/* ask before letting go of the area the stream has: a refusal must leave the table encoder its scratch */
 		void *p = dev_alloc(h, need);
@@ -2329,6 +2487,10 @@ int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, si
 	if (h->trace >= 1)
 		fprintf(stderr, "[gpumt brotli win] records %zu depth %u plane %zu fallback %d\n", nrec, win ? depth : 0u,
 			win ? (size_t)4 * slice_in : (size_t)0, win ? 0 : 1);
+	if (h->trace >= 1 && win && seg_log)
+		fprintf(stderr, "[gpumt win chain] segments %zu seg_log %d heads %zu serial %d\n",
+			pheads ? slice_rec * (((slice_in < chunk ? slice_in : chunk) + ((size_t)1 << seg_log) - 1) >> seg_log) : slice_rec,
+			seg_log, pheads, par ? 0 : 1);
 	if (!win)
 		return gpumt_brotli_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, s);
 	u32 *blk_len = (u32 *)h->scratch[0][s];
@@ -2341,8 +2503,10 @@ int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, si
 		const unsigned eg = (unsigned)(nb < egrid ? nb : egrid), cg = (unsigned)(nr < cgrid ? nr : cgrid);
 		const u8 *in = (const u8 *)d_in + i0;
 		u8 *slots = (u8 *)d_slots + r0 * slot_stride;
-		hipLaunchKernelGGL(zmt_zstd_win_chain_kernel, dim3(cg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nr, plane,
-				   heads);
+		const int rc = win_chain_launch(h, in, ni, chunk, nr, plane, heads, cg, par ? (u32 *)((u8 *)h->scratch[0][s] + need) : NULL,
+						seg_log, s);
+		if (rc)
+			return rc;
 		hipLaunchKernelGGL(zmt_brotli_enc_win_kernel, dim3(eg), dim3(64), 0, h->st[s], in, (u64)ni, (u32)chunk, (u32)nb, bpr,
 				   slots, (u64)slot_stride, blk_len, seqbuf, (const u32 *)plane, depth);
 		hipLaunchKernelGGL(zmt_brotli_assemble_kernel, dim3((unsigned)nr), dim3(256), 0, h->st[s], (u64)ni, (u32)chunk, (u32)nr,
@@ -2577,6 +2741,17 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 		prev = h->bwin_cap_mb;
 		h->bwin_cap_mb = variant;
 		h->bwin_refused = 0; /* (a new cap: ask again) */
+	} else if (!strcmp(what, "win_chain_par")) {
+		if (variant != 0 && variant != 1 && (variant < 12 || variant > 24))
+			return -1;
+		prev = h->wchain_par;
+		h->wchain_par = variant;
+	} else if (!strcmp(what, "win_chain_cap_mb")) {
+		if (variant < 0)
+			return -1;
+		prev = h->wchain_cap_mb;
+		h->wchain_cap_mb = variant;
+		h->wchain_refused = 0; /* (a new cap: ask again) */
 	} else if (!strcmp(what, "lz4_run_par")) {
 		if (variant != 0 && variant != 1)
 			return -1;

@@ -876,6 +876,7 @@ static __device__ u32 ze_huf_encode(ZEncLds &L, u32 *stage, const ZHuf hf, const
 	} while (0)
 
 #include "zstd_enc_win.h"
+#include "enc_win_chain_par.h"
 
 /* WIN: the match finder is ze_win_find over the chunk's chain plane (zstd_enc_win.h) instead of the LDS table; a candidate
  * may then lie in an earlier block of the chunk (a block-relative position below 0, see ze_at) */
@@ -1762,11 +1763,83 @@ void emu_zstd_win_chain(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 grid)
 	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1}, [=]() { zmt_zstd_win_chain_kernel(in, n, chunk, nrec, plane, hd); });
 }
 
+/* ---- the plane in segments (enc_win_chain_par.h) ---- */
+#define GPUMT_WIN_CHAIN_SEG_DEFAULT 20 /* as gpumt.hip */
+
+/* the head-table bytes of the segment build, as gpumt_win_chain_par_scratch: 0 = no chunk has more than one segment */
+u64 emu_win_chain_par_scratch(u64 n, u32 chunk, u32 seg_log)
+{
+	const u64 cl = n < chunk ? n : chunk, spc = (cl + ((u64)1 << seg_log) - 1) >> seg_log;
+	if (spc <= 1)
+		return 0;
+	return ((n + chunk - 1) / chunk * spc * 4) << zw_hlog((u32)cl);
+}
+
+/* the chain plane through the three launches; seg_log 12..24.  Where no chunk has more than one segment the serial
+ * kernel runs, as on the device */
+void emu_win_chain_par(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 seg_log, u32 grid)
+{
+	const u64 bytes = emu_win_chain_par_scratch(n, chunk, seg_log);
+	if (!bytes) {
+		emu_zstd_win_chain(in, n, chunk, plane, grid);
+		return;
+	}
+	const u32 cl = (u32)(n < chunk ? n : chunk), spc = (u32)(((u64)cl + ((u64)1 << seg_log) - 1) >> seg_log);
+	const u32 nrec = (u32)((n + chunk - 1) / chunk), nseg = nrec * spc, hslog = zw_hlog(cl);
+	std::vector<u32> heads((size_t)(bytes / 4), 0xA5A5A5A5u); /* scratch starts as garbage: exactly the bytes asked for */
+	u32 *hd = heads.data();
+	if (grid > nseg)
+		grid = nseg;
+	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1},
+		    [=]() { zmt_win_chain_seg_kernel(in, n, chunk, seg_log, spc, nseg, hslog, plane, hd); });
+	emu::launch(emu::dim3{(u32)(((u64)nrec << hslog) / 256), 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_win_chain_carry_kernel(n, chunk, seg_log, spc, nrec, hslog, hd); });
+	emu::launch(emu::dim3{(u32)((n + 255) / 256), 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_win_chain_patch_kernel(in, n, chunk, seg_log, spc, hslog, plane, hd); });
+}
+
+/* GPUMT_WIN_CHAIN_PAR as gpumt_open reads it (0 = off, 1 = the default segment, 12..24; unset, empty and any other text =
+ * off) and GPUMT_WIN_CHAIN_CAP, the head-table bytes the "device" grants (0 = any) */
+void emu_win_chain_env(u32 *seg_log, u64 *cap)
+{
+	const char *e = getenv("GPUMT_WIN_CHAIN_PAR"), *c = getenv("GPUMT_WIN_CHAIN_CAP");
+	char *end = nullptr;
+	const long v = e && *e ? strtol(e, &end, 10) : 0;
+	*seg_log = !e || !*e || *end ? 0u : v == 1 ? (u32)GPUMT_WIN_CHAIN_SEG_DEFAULT : v >= 12 && v <= 24 ? (u32)v : 0u;
+	*cap = c && *c ? strtoull(c, 0, 10) : 0;
+}
+
+/* the plane of both emulated _win calls: seg_log 0 = the serial kernel, as before; else the segment build unless its head
+ * tables exceed chain_cap.  info = segments, head-table bytes asked for, 1 where the serial kernel built the plane */
+void emu_win_chain_build(const u8 *in, u64 n, u32 chunk, u32 *plane, u32 grid, u32 seg_log, u64 chain_cap, u64 info[3])
+{
+	const u64 nrec = n ? (n + chunk - 1) / chunk : 1, heads = seg_log ? emu_win_chain_par_scratch(n, chunk, seg_log) : 0;
+	const int par = heads && !(chain_cap && heads > chain_cap);
+	if (par)
+		emu_win_chain_par(in, n, chunk, plane, seg_log, grid);
+	else
+		emu_zstd_win_chain(in, n, chunk, plane, grid);
+	info[0] = heads ? nrec * (((n < chunk ? n : chunk) + ((u64)1 << seg_log) - 1) >> seg_log) : nrec;
+	info[1] = heads;
+	info[2] = !par;
+}
+
+static u32 emu_zstd_compress_batch_win_chain(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid,
+					     int level, u32 depth, u64 cap, u32 seg_log, u64 chain_cap, u64 info[3]);
+
 /* depth: 0 = by level.  cap: the scratch the "device" grants, 0 = any -- a request above it is refused and the call
  * encodes with the table encoder of the level, as below level 10 and for chunks above 128 MiB.  Returns the depth the
  * window encoder ran with, 0 where the table encoder ran */
 u32 emu_zstd_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level,
 				u32 depth, u64 cap)
+{
+	u64 info[3];
+	return emu_zstd_compress_batch_win_chain(in, n, chunk, slots, stride, rec_len, grid, level, depth, cap, 0, 0, info);
+}
+
+/* the same with the plane built by emu_win_chain_build(seg_log, chain_cap) */
+static u32 emu_zstd_compress_batch_win_chain(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid,
+					     int level, u32 depth, u64 cap, u32 seg_log, u64 chain_cap, u64 info[3])
 {
 	const u32 nrec = n ? (u32)((n + chunk - 1) / chunk) : 1;
 	const u32 bpr = (chunk + ZE_BLOCK - 1) / ZE_BLOCK;
@@ -1784,7 +1857,7 @@ u32 emu_zstd_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 s
 	std::vector<u8> seq((size_t)grid * ZE_WSCRATCH, 0xA5);
 	u32 *bl = blk_len.data(), *pl = plane.data();
 	u8 *sq = seq.data();
-	emu_zstd_win_chain(in, n, chunk, pl, grid);
+	emu_win_chain_build(in, n, chunk, pl, grid, seg_log, chain_cap, info);
 	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1},
 		    [=]() { zmt_zstd_enc_win_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq, pl, depth); });
 	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{256, 1, 1},
@@ -1793,7 +1866,8 @@ u32 emu_zstd_compress_batch_win(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 s
 }
 
 /* (the emulated boundary keeps no variants: GPUMT_ZSTD_WIN_DEPTH and GPUMT_ZSTD_WIN_CAP -- bytes -- stand in for
- * gpumt_set_variant's "zstd_win_depth" and "zstd_win_cap_mb") */
+ * gpumt_set_variant's "zstd_win_depth" and "zstd_win_cap_mb", GPUMT_WIN_CHAIN_PAR and GPUMT_WIN_CHAIN_CAP -- bytes -- for
+ * "win_chain_par" and "win_chain_cap_mb") */
 int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
 				  uint32_t *d_rec_len, int level, int s)
 {
@@ -1805,11 +1879,17 @@ int gpumt_zstd_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, size
 	const u64 cap = c && *c ? strtoull(c, 0, 10) : 0;
 	if (dv < 0 || dv > 256)
 		return GPUMT_E_ARG;
-	const u32 ran = emu_zstd_compress_batch_win((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3, level,
-						    (u32)dv, cap);
+	u32 seg_log;
+	u64 chain_cap, info[3];
+	emu_win_chain_env(&seg_log, &chain_cap);
+	const u32 ran = emu_zstd_compress_batch_win_chain((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3,
+							  level, (u32)dv, cap, seg_log, chain_cap, info);
 	if (t && atoi(t) >= 1 && level >= 10)
 		fprintf(stderr, "[gpumt zstd win] records %zu depth %u plane %zu fallback %d\n", n ? (n + chunk - 1) / chunk : (size_t)1, ran,
 			ran ? (size_t)4 * n : (size_t)0, ran ? 0 : 1);
+	if (t && atoi(t) >= 1 && ran && seg_log)
+		fprintf(stderr, "[gpumt win chain] segments %zu seg_log %u heads %zu serial %d\n", (size_t)info[0], seg_log, (size_t)info[1],
+			(int)info[2]);
 	return GPUMT_OK;
 }
 }

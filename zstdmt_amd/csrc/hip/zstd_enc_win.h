@@ -31,6 +31,36 @@ static __device__ __forceinline__ u32 zw_hlog(u32 clen)
 	return (u32)(l > ZW_HLOG_MAX ? ZW_HLOG_MAX : l < ZW_HLOG_MIN ? ZW_HLOG_MIN : l);
 }
 
+/* One step of the chain build: the 64 positions from p0 (a multiple of 64 inside the chunk of clen bytes at base) are hashed
+ * and linked in position order through `head`, 1 << hlog words.  Shared by the serial kernel below and the segment kernel
+ * of enc_win_chain_par.h, so both write the same words wherever their head tables agree. */
+static __device__ __forceinline__ void zw_chain_step(const u8 *__restrict__ base, u32 clen, u32 hlog, u32 p0, int lane,
+						     u32 *__restrict__ prev, u32 *__restrict__ head)
+{
+	const u32 p = p0 + (u32)lane;
+	/* (reads up to 7 bytes behind the chunk: the next chunk's, or the input's slack, include/gpumt.h) */
+	const u64 v = ld64u(base + (p < clen ? p : clen - 1));
+	const bool ok = p + ZE_HBYTES <= clen; /* the last ZE_HBYTES - 1 positions have no hash */
+	const u32 h = ze_hash<ZE_HBYTES, ZW_HLOG_MAX>(v) >> (ZW_HLOG_MAX - hlog);
+	const u32 e = head[ok ? h : 0u];
+	/* the lanes of this step with my hash: one ballot per hash bit.  A lane chains to the nearest such lane
+	 * below it and only the first of them to the table's entry; the highest writes the head -- so the plane
+	 * does not depend on the order the memory serves the lanes in */
+	u64 same = wv_ballot(ok);
+	for (u32 b = 0; b < hlog; b++) {
+		const bool bit = (h >> b) & 1u;
+		const u64 m = wv_ballot(bit);
+		same &= bit ? m : ~m;
+	}
+	const u64 lower = same & ((1ull << lane) - 1ull), higher = (same >> lane) >> 1;
+	if (p < clen)
+		prev[p] = !ok ? ZW_NONE : lower ? p0 + 63u - (u32)__builtin_clzll(lower) : e;
+	if (ok && !higher)
+		head[h] = p;
+	wave_mem_fence(); /* the next step reads what this one wrote */
+	wv_sync();
+}
+
 extern "C" __global__ void __launch_bounds__(64)
 zmt_zstd_win_chain_kernel(const u8 *__restrict__ in, u64 n, u32 chunk, u32 nrec, u32 *__restrict__ plane,
 			  u32 *__restrict__ heads)
@@ -49,30 +79,8 @@ zmt_zstd_win_chain_kernel(const u8 *__restrict__ in, u64 n, u32 chunk, u32 nrec,
 			head[i] = ZW_NONE;
 		wave_mem_fence();
 		wv_sync();
-		for (u32 p0 = 0; p0 < clen; p0 += 64) {
-			const u32 p = p0 + (u32)lane;
-			/* (reads up to 7 bytes behind the chunk: the next chunk's, or the input's slack, include/gpumt.h) */
-			const u64 v = ld64u(base + (p < clen ? p : clen - 1));
-			const bool ok = p + ZE_HBYTES <= clen; /* the last ZE_HBYTES - 1 positions have no hash */
-			const u32 h = ze_hash<ZE_HBYTES, ZW_HLOG_MAX>(v) >> (ZW_HLOG_MAX - hlog);
-			const u32 e = head[ok ? h : 0u];
-			/* the lanes of this step with my hash: one ballot per hash bit.  A lane chains to the nearest such lane
-			 * below it and only the first of them to the table's entry; the highest writes the head -- so the plane
-			 * does not depend on the order the memory serves the lanes in */
-			u64 same = wv_ballot(ok);
-			for (u32 b = 0; b < hlog; b++) {
-				const bool bit = (h >> b) & 1u;
-				const u64 m = wv_ballot(bit);
-				same &= bit ? m : ~m;
-			}
-			const u64 lower = same & ((1ull << lane) - 1ull), higher = (same >> lane) >> 1;
-			if (p < clen)
-				prev[p] = !ok ? ZW_NONE : lower ? p0 + 63u - (u32)__builtin_clzll(lower) : e;
-			if (ok && !higher)
-				head[h] = p;
-			wave_mem_fence(); /* the next step reads what this one wrote */
-			wv_sync();
-		}
+		for (u32 p0 = 0; p0 < clen; p0 += 64)
+			zw_chain_step(base, clen, hlog, p0, lane, prev, head);
 	}
 }
 

@@ -430,6 +430,24 @@ class Engine:
     def zstd_win_depth(self, level):
         return int(self.L.gpumt_zstd_win_depth(int(level)))
 
+    def win_chain_plane(self, data: bytes, chunk, seg_log=0):
+        """gpumt_win_chain_plane over host bytes -> the chain plane of the window encoders, one u32 per byte; seg_log 0 =
+        one wave per chunk, 12..24 = in segments of 1 << seg_log positions.  Refused head tables raise NativeError"""
+        n = len(data)
+        d_in = self.upload(data)
+        d_pl = self.upload(np.full(n + 1, 0xA5A5A5A5, np.uint32), slack=0)
+        try:
+            self._ck(self.L.gpumt_win_chain_plane(self.h, d_in.ptr, n, int(chunk), d_pl.ptr, int(seg_log), 0), "win_chain_plane")
+            plane = self.download(d_pl, 4 * (n + 1), np.uint32)
+        finally:
+            d_in.free()
+            d_pl.free()
+        assert int(plane[n]) == 0xA5A5A5A5, "the chain build wrote past the end of the plane"
+        return plane[:n]
+
+    def win_chain_par_scratch(self, n, chunk, seg_log):
+        return int(self.L.gpumt_win_chain_par_scratch(int(n), int(chunk), int(seg_log)))
+
     def zstd_probe(self, d_stream, d_rec_off, d_rec_len, nrec, d_out_len, d_out_off, d_status, stream=0):
         self._ck(self.L.gpumt_zstd_probe_sizes(self.h, d_stream.ptr, d_rec_off.ptr, d_rec_len.ptr, nrec,
                                                d_out_len.ptr, d_out_off.ptr, d_status.ptr, stream),
