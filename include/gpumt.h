@@ -678,6 +678,55 @@ int gpumt_brotli_decompress_batch(gpumt_ctx *h, const void *d_stream, const uint
 				  const uint64_t *d_out_off, const uint32_t *d_out_cap,
 				  uint32_t *d_out_len, uint32_t *d_status, int stream);
 
+/*
+ * Records that say where they can be cut, and a decoder that spreads such a record over many waves (both opt-in; what
+ * GPUMT_BROTLI_INDEX=1 and GPUMT_BROTLI_REC_PAR=1 make BROTLIMT_compressCCtx and BROTLIMT_decompressDCtx call).
+ *
+ * gpumt_brotli_compress_batch_index: gpumt_brotli_compress_batch_level -- same arguments, same block encoders -- with a span
+ * index in every record of two blocks or more.  The index is one metadata meta-block (RFC 7932 section 9.2: every decoder
+ * skips it) directly in front of the closing 0x03 byte.  It starts byte-aligned: ISLAST 0, MNIBBLES 11, reserved 0,
+ * MSKIPBYTES nb, MSKIPLEN - 1 in nb bytes (the least nb that holds it), zero bits to the byte boundary -- nb + 1 bytes --
+ * then, little endian, n entries { u32 comp_bytes, u32 out_bytes } and the trailer { u32 n, u32 0x58495242 "BRIX" }.  Span k
+ * is stream bytes [sum comp_bytes[<k], + comp_bytes[k]) and decodes to out_bytes[k] bytes; span 0 starts at stream byte 0 with
+ * the WBITS bits; one span is one 128 KiB block with its padding meta-block.  A reader finds the index from the record's
+ * end: the last byte 0x03, the trailer in front of it, the body of 8 n + 8 bytes, the header.  The table encoders leave
+ * every block self-contained (no match source and no reused distance from before the block), which is what makes the cut
+ * valid; the window encoder (gpumt_brotli_compress_batch_win) does not, and writes no index.  A record of one block (and
+ * the empty record) is byte for byte gpumt_brotli_compress_batch_level's.  The index costs 8 bytes per block and at most 12
+ * more; csize in the 16-byte header includes it, the hint is unchanged, and gpumt_zstd_slot_stride(chunk) holds the record
+ * at every chunk size (12 spare bytes per block, 15 per record); a record of more than 65536 blocks gets none.
+ *
+ * gpumt_brotli_decompress_batch_par: gpumt_brotli_decompress_batch -- same arguments, same d_status, d_out_len and output
+ * bytes for every batch -- plus d_rec_par (nrec words, or NULL): 1 where the span stages produced the record, 0 where the
+ * record decoders did.  The index is a hint and is never trusted.  Stages (csrc/hip/brotli_dec_rec.h, which also holds the
+ * equivalence argument):
+ *   plan     one lane per record: the index from the record's end, and its checks -- the magic, min_spans <= n <= 65536, no
+ *            zero entry, sum comp_bytes + index block + 1 == d_rec_len, the bytes at sum comp_bytes are exactly the header
+ *            above, sum out_bytes <= d_out_cap, WBITS.  A record that fails any of them is not eligible; no verdict here.
+ *   table    the spans of all eligible records as units (stream range, output offset, WBITS), in slices of 2^20 units.
+ *   execute  the dec4 scheme with a span as the unit: four spans per wave, one 16-lane group each, from the span's first
+ *            byte to its last exactly, on a meta-block boundary.  A group refuses -- not a verdict -- what dec4 hands over
+ *            (context modelling, block switching, large distance alphabets), an ISLAST bit inside the span, a meta-block
+ *            across the span's end, a decoded length other than out_bytes, a copy whose source lies before the span's
+ *            first output byte (every static dictionary reference is one) and, behind span 0, a distance code that
+ *            reads a ring entry the span did not write.
+ *   finish   a record is kept only if every span ended without refusal: d_out_len = sum out_bytes, GPUMT_ST_OK, d_rec_par 1.
+ *   records  the pair of gpumt_brotli_decompress_batch over the whole batch, passing kept records by: every record not kept
+ *            is decoded and judged there, so the verdicts are the serial call's by construction.
+ * One host round trip (the plans, 32 bytes per record).  Own scratch: 36 bytes per record and 36 per span of the largest
+ * slice; refused (or above "brotli_rec_cap_mb"), the whole batch goes to gpumt_brotli_decompress_batch and the size is
+ * remembered.  gpumt_set_variant: "brotli_rec_par" (1 / 0 = the serial call alone), "brotli_rec_min_spans" (2..65536;
+ * default 2 -- see profiles/brotli_rec_par.txt), "brotli_rec_cap_mb" (0 = none); anything else returns -1 and changes nothing.
+ * GPUMT_TRACE=1 prints per call `[gpumt brotli rec] records N par P spans S kept K fallback F` (P eligible records, S their
+ * spans, K records kept, F = 1 when scratch was refused).
+ */
+int gpumt_brotli_compress_batch_index(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
+				      size_t slot_stride, uint32_t *d_rec_len, int level, int stream);
+int gpumt_brotli_decompress_batch_par(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off,
+				      const uint32_t *d_rec_len, size_t nrec, void *d_out,
+				      const uint64_t *d_out_off, const uint32_t *d_out_cap,
+				      uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int stream);
+
 /* ---- snappy-mt records (16-byte header + one raw snappy stream, lib/snappy-mt_compress.c:280-300) ----
  *
  * gpumt_snappy_compress_batch: chunk i = d_in[i*chunk, ...) -> one record (header with the payload size,

@@ -82,6 +82,8 @@ GPUMT_SYMBOLS = {
     "gpumt_brotli_win_depth": (_i, [_i]),
     "gpumt_brotli_compress_batch_win": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i, _i]),
     "gpumt_brotli_decompress_batch": (_i, [_vp, _vp, _u64p, _u32p, _sz, _vp, _u64p, _u32p, _u32p, _u32p, _i]),
+    "gpumt_brotli_compress_batch_index": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i, _i]),
+    "gpumt_brotli_decompress_batch_par": (_i, [_vp, _vp, _u64p, _u32p, _sz, _vp, _u64p, _u32p, _u32p, _u32p, _u32p, _i]),
     "gpumt_snappy_slot_stride": (_sz, [_sz]),
     "gpumt_snappy_compress_batch": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _u32p, _i]),
     "gpumt_snappy_decompress_batch": (_i, [_vp, _vp, _u64p, _u32p, _sz, _vp, _u64p, _u32p, _u32p, _u32p, _i]),

@@ -30,6 +30,8 @@
 #include <cstddef>
 #include "lz4_common.h"
 #include "lz4_frame.h"
+#define BREC_HOST_ONLY /* the index layout alone */
+#include "brotli_dec_rec.h"
 
 #define BE_BLOCK 131072u
 #define BE_BSTRIDE (BE_BLOCK + 16u) /* area of one block inside a record slot (same as zstd's) */
@@ -874,10 +876,12 @@ zmt_brotli_enc_win_kernel(BE_KERNEL_ARGS, const u32 *__restrict__ plane, u32 dep
 
 /* ---------------------------------------------------------------------------------------------
  * Record assembly: 16-byte brotli-mt header (lib/brotli-mt_compress.c:285-304: skippable magic, 8,
- * compressed size, "BR", hint), the chunk's blocks moved together, the closing empty last meta-block. */
-extern "C" __global__ void __launch_bounds__(256)
-zmt_brotli_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__restrict__ slots, u64 stride,
-			   const u32 *__restrict__ blk_len, u32 *__restrict__ rec_len)
+ * compressed size, "BR", hint), the chunk's blocks moved together, the closing empty last meta-block.
+ * INDEX (gpumt_brotli_compress_batch_index): a record of two blocks or more gets the span index of brotli_dec_rec.h in
+ * front of the closing byte -- one span per block, which the table encoders leave self-contained. */
+template <bool INDEX>
+static __device__ __forceinline__ void be_assemble(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__restrict__ slots, u64 stride,
+						   const u32 *__restrict__ blk_len, u32 *__restrict__ rec_len)
 {
 	const u32 rec = blockIdx.x, t = threadIdx.x;
 	if (rec >= nrec)
@@ -916,6 +920,32 @@ zmt_brotli_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__re
 		}
 		at += len;
 	}
+	/* (the slot holds it: a block fills at most BE_BLOCK + 4 of its BE_BSTRIDE bytes, which leaves 12 bytes per block for
+	 * the entry's 8 and 15 more for the 12 of header and trailer; a record that would not fit all the same stays as it was) */
+	if (INDEX && nb >= 2u && nb <= BREC_MAX_SPANS && (u64)at + BREC_INDEX_BYTES(nb) + 1u <= stride) {
+		u8 *d = slot + at;
+		const u32 hb = BREC_NB(nb) + 1u;
+		if (t == 0) {
+			const u32 hv = BREC_HEADER(nb);
+			for (u32 k = 0; k < hb; k++)
+				d[k] = (u8)(hv >> (8 * k));
+			u8 *tr = d + hb + 8u * nb;
+			for (u32 k = 0; k < 4; k++) {
+				tr[k] = (u8)(nb >> (8 * k));
+				tr[4 + k] = (u8)(BREC_MAGIC >> (8 * k));
+			}
+		}
+		for (u32 b = t; b < nb; b += 256) {
+			const u32 c = blk_len[(u64)rec * blk_per_rec + b];
+			const u32 o = b + 1 < nb ? BE_BLOCK : clen - b * BE_BLOCK;
+			u8 *e = d + hb + 8u * b;
+			for (u32 k = 0; k < 4; k++) {
+				e[k] = (u8)(c >> (8 * k));
+				e[4 + k] = (u8)(o >> (8 * k));
+			}
+		}
+		at += BREC_INDEX_BYTES(nb);
+	}
 	if (t == 0) {
 		if (nb == 0) {
 			slot[at++] = 0x33; /* WBITS = 18 (bits 1,1,0,0), ISLAST, ISLASTEMPTY: the empty stream */
@@ -935,6 +965,19 @@ zmt_brotli_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__re
 		slot[14] = (u8)hint; slot[15] = (u8)(hint >> 8);
 		rec_len[rec] = at;
 	}
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+zmt_brotli_assemble_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__restrict__ slots, u64 stride,
+			   const u32 *__restrict__ blk_len, u32 *__restrict__ rec_len)
+{
+	be_assemble<false>(n, chunk, nrec, blk_per_rec, slots, stride, blk_len, rec_len);
+}
+extern "C" __global__ void __launch_bounds__(256)
+zmt_brotli_assemble_index_kernel(u64 n, u32 chunk, u32 nrec, u32 blk_per_rec, u8 *__restrict__ slots, u64 stride,
+				 const u32 *__restrict__ blk_len, u32 *__restrict__ rec_len)
+{
+	be_assemble<true>(n, chunk, nrec, blk_per_rec, slots, stride, blk_len, rec_len);
 }
 
 #ifdef ZMT_EMU
@@ -994,6 +1037,41 @@ static u32 emu_brotli_compress_batch_win_chain(const u8 *in, u64 n, u32 chunk, u
 	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{256, 1, 1},
 		    [=]() { zmt_brotli_assemble_kernel(n, chunk, nrec, bpr, slots, stride, bl, rec_len); });
 	return depth;
+}
+
+/* gpumt_brotli_compress_batch_index: the block encoder of the quality's tier (as emu_brotli_compress_batch_level), then
+ * the assembly that writes the span index */
+void emu_brotli_compress_batch_index(const u8 *in, u64 n, u32 chunk, u8 *slots, u64 stride, u32 *rec_len, u32 grid, int level)
+{
+	const u32 nrec = n ? (u32)((n + chunk - 1) / chunk) : 1;
+	const u32 bpr = (chunk + BE_BLOCK - 1) / BE_BLOCK;
+	const u32 nblk = nrec * bpr;
+	if (grid > nblk)
+		grid = nblk;
+	std::vector<u32> blk_len(nblk, 0xA5A5A5A5u);
+	std::vector<u8> seq((size_t)grid * BE_WSCRATCH, 0xA5);
+	u32 *bl = blk_len.data();
+	u8 *sq = seq.data();
+	emu::launch(emu::dim3{grid, 1, 1}, emu::dim3{64, 1, 1}, [=]() {
+		if (level <= 3)
+			zmt_brotli_enc_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq);
+		else if (level <= 8)
+			zmt_brotli_enc_t2_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq);
+		else
+			zmt_brotli_enc_t3_kernel(in, n, chunk, nblk, bpr, slots, stride, bl, sq);
+	});
+	emu::launch(emu::dim3{nrec, 1, 1}, emu::dim3{256, 1, 1},
+		    [=]() { zmt_brotli_assemble_index_kernel(n, chunk, nrec, bpr, slots, stride, bl, rec_len); });
+}
+
+int gpumt_brotli_compress_batch_index(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
+				      uint32_t *d_rec_len, int level, int s)
+{
+	if (!h || s < 0 || s >= GPUMT_NSTREAMS || chunk == 0 || chunk > 0x40000000u || slot_stride < emu_zstd_slot_stride(chunk) ||
+	    level < 0 || level > 11)
+		return GPUMT_E_ARG;
+	emu_brotli_compress_batch_index((const u8 *)d_in, n, (u32)chunk, (u8 *)d_slots, slot_stride, d_rec_len, 3, level);
+	return GPUMT_OK;
 }
 
 /* (the emulated boundary keeps no variants: GPUMT_BROTLI_WIN_DEPTH and GPUMT_BROTLI_WIN_CAP -- bytes -- stand in for

@@ -23,6 +23,9 @@ typedef uint64_t u64;
 /* ... and of gpumt_lz4_decompress_batch_par */
 #define LREC_HOST_ONLY
 #include "lz4_dec_rec.h"
+/* ... and of gpumt_brotli_decompress_batch_par */
+#define BREC_HOST_ONLY
+#include "brotli_dec_rec.h"
 
 extern "C" {
 __global__ void zmt_xxh32_kernel(const u8 *, const u64 *, const u32 *, u32, u32 *, const u32 *,
@@ -142,6 +145,14 @@ __global__ void zmt_snappy_dec_kernel(const u8 *, const u64 *, const u32 *, u32,
 __global__ void zmt_snappy_dec2_kernel(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *, const u32 *, u32 *, u32 *);
 __global__ void zmt_brotli_enc_win_kernel(const u8 *, u64, u32, u32, u32, u8 *, u64, u32 *, u8 *, const u32 *, u32);
 __global__ void zmt_brotli_assemble_kernel(u64, u32, u32, u32, u8 *, u64, const u32 *, u32 *);
+__global__ void zmt_brotli_assemble_index_kernel(u64, u32, u32, u32, u8 *, u64, const u32 *, u32 *);
+__global__ void zmt_brotli_rec_plan_kernel(const u8 *, const u64 *, const u32 *, u32, const u64 *, const u32 *, u32, BRec *);
+__global__ void zmt_brotli_rec_scan_kernel(const BRec *, u32, u32 *);
+__global__ void zmt_brotli_rec_table_kernel(const u8 *, const BRec *, u32, u32, const u32 *, u32, B4Span *);
+__global__ void zmt_brotli_rec_finish_kernel(const BRec *, u32, const u32 *, u32, const B4Span *, const u32 *, u32 *, u32 *, u32 *);
+__global__ void zmt_brotli_dec4_wanted_kernel(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *, const u32 *,
+					      u32 *, u32 *, u32);
+__global__ void zmt_brotli_dec4_span_kernel(const u8 *, const B4Span *, u32, u8 *, u32 *);
 __global__ void zmt_brotli_dec_kernel(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *, const u32 *,
 				      u32 *, u32 *, u8 *, const u8 *, u32);
 __global__ void zmt_brotli_dec_kernel_prof(const u8 *, const u64 *, const u32 *, u32, u8 *, const u64 *,
@@ -257,6 +268,17 @@ struct gpumt_ctx {
 	size_t lrec_tab_bytes[GPUMT_NSTREAMS];
 	void *lrec_pin[GPUMT_NSTREAMS]; /* pinned copy of the per-record counts, for the host to cut slices */
 	size_t lrec_pin_bytes[GPUMT_NSTREAMS];
+	/* the same of gpumt_brotli_decompress_batch_par (brotli_dec_rec.h) */
+	int brec_par;       /* 1 = indexed brotli-mt records span by span; 0 = the record decoders alone */
+	int brec_min_spans; /* records of fewer spans stay with the record decoders */
+	int brec_cap_mb;
+	size_t brec_refused;
+	void *brec_area[GPUMT_NSTREAMS]; /* per record: the plan and the first span */
+	size_t brec_bytes[GPUMT_NSTREAMS];
+	void *brec_tab[GPUMT_NSTREAMS]; /* per slice: the span table and a status word per span */
+	size_t brec_tab_bytes[GPUMT_NSTREAMS];
+	void *brec_pin[GPUMT_NSTREAMS];
+	size_t brec_pin_bytes[GPUMT_NSTREAMS];
 	int sdec_variant; /* snappy decoder: 0 = element by element, 1 = 64 elements per batch (snappy.hip) */
 	int bdec_variant; /* brotli decoder: 0 = by batch size, 1 = the general kernel only, 2 = dec4 (four records per wave) + general for what it hands over */
 	int bdec_waves;   /* resident waves of the persistent brotli decoder kernel (whole device) */
@@ -481,6 +503,18 @@ int gpumt_open(int device, gpumt_ctx **out)
 					*(k == 0 ? &h->lrec_seg : k == 1 ? &h->lrec_min_blocks : &h->lrec_slice_blocks) = (int)v;
 			}
 		}
+		/* gpumt_brotli_decompress_batch_par: GPUMT_BROTLI_REC_MIN_SPANS (2..65536) */
+		h->brec_par = 1;
+		h->brec_min_spans = 2; /* profiles/brotli_rec_par.txt */
+		e = getenv("GPUMT_BROTLI_REC_MIN_SPANS");
+		if (e && *e) {
+			char *end;
+			const long v = strtol(e, &end, 10);
+			if (*end || v < 2 || v > 65536)
+				fprintf(stderr, "gpumt: GPUMT_BROTLI_REC_MIN_SPANS=%s ignored (2..65536)\n", e);
+			else
+				h->brec_min_spans = (int)v;
+		}
 		/* GPUMT_WIN_CHAIN_PAR: the window encoders' chain plane in segments (gpumt_set_variant "win_chain_par": 1 or
 		 * 12..24); unset, empty and any other text = off */
 		e = getenv("GPUMT_WIN_CHAIN_PAR");
@@ -528,6 +562,12 @@ void gpumt_close(gpumt_ctx *h)
 			dev_free(h, h->lrec_tab[i]);
 		if (h->lrec_pin[i])
 			(void)hipHostFree(h->lrec_pin[i]);
+		if (h->brec_area[i])
+			dev_free(h, h->brec_area[i]);
+		if (h->brec_tab[i])
+			dev_free(h, h->brec_tab[i]);
+		if (h->brec_pin[i])
+			(void)hipHostFree(h->brec_pin[i]);
 	}
 	for (int i = 0; i < NTIMERS; i++) {
 		(void)hipEventDestroy(h->t0[i]);
@@ -2371,8 +2411,24 @@ int gpumt_brotli_compress_batch(gpumt_ctx *h, const void *d_in, size_t n, size_t
 	return gpumt_brotli_compress_batch_level(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, 1, s);
 }
 
+static int brotli_compress_tables(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
+				  uint32_t *d_rec_len, int level, int index, int s);
+
 int gpumt_brotli_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
 				      size_t slot_stride, uint32_t *d_rec_len, int level, int s)
+{
+	return brotli_compress_tables(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, 0, s);
+}
+
+/* the same records with the span index of brotli_dec_rec.h in those of two blocks or more */
+int gpumt_brotli_compress_batch_index(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots,
+				      size_t slot_stride, uint32_t *d_rec_len, int level, int s)
+{
+	return brotli_compress_tables(h, d_in, n, chunk, d_slots, slot_stride, d_rec_len, level, 1, s);
+}
+
+static int brotli_compress_tables(gpumt_ctx *h, const void *d_in, size_t n, size_t chunk, void *d_slots, size_t slot_stride,
+				  uint32_t *d_rec_len, int level, int index, int s)
 {
 	if (!h || !STREAM_OK(s) || chunk == 0 || chunk > 0x40000000u || slot_stride < gpumt_zstd_slot_stride(chunk) ||
 	    level < 0 || level > 11)
@@ -2413,9 +2469,14 @@ int gpumt_brotli_compress_batch_level(gpumt_ctx *h, const void *d_in, size_t n, 
 	else
 		hipLaunchKernelGGL(zmt_brotli_enc_t3_kernel, dim3(grid), dim3(64), 0, h->st[s], (const u8 *)d_in, (u64)n,
 				   (u32)chunk, (u32)nblk, bpr, (u8 *)d_slots, (u64)slot_stride, blk_len, seqbuf);
-	hipLaunchKernelGGL(zmt_brotli_assemble_kernel, dim3((unsigned)nrec), dim3(256), 0, h->st[s], (u64)n,
-			   (u32)chunk, (u32)nrec, bpr, (u8 *)d_slots, (u64)slot_stride, (const u32 *)blk_len,
-			   d_rec_len);
+	if (index)
+		hipLaunchKernelGGL(zmt_brotli_assemble_index_kernel, dim3((unsigned)nrec), dim3(256), 0, h->st[s], (u64)n,
+				   (u32)chunk, (u32)nrec, bpr, (u8 *)d_slots, (u64)slot_stride, (const u32 *)blk_len,
+				   d_rec_len);
+	else
+		hipLaunchKernelGGL(zmt_brotli_assemble_kernel, dim3((unsigned)nrec), dim3(256), 0, h->st[s], (u64)n,
+				   (u32)chunk, (u32)nrec, bpr, (u8 *)d_slots, (u64)slot_stride, (const u32 *)blk_len,
+				   d_rec_len);
 	PROF1(9);
 	CK(hipGetLastError());
 	return GPUMT_OK;
@@ -2519,10 +2580,23 @@ int gpumt_brotli_compress_batch_win(gpumt_ctx *h, const void *d_in, size_t n, si
 
 extern "C" const unsigned char zmt_brotli_static[], zmt_brotli_static_end[];
 
+/* the record decoders: every record (only = 0xFFFFFFFF), or the records whose d_status is `only` on entry */
+static int brotli_decompress_records(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off, const uint32_t *d_rec_len,
+				     size_t nrec, void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+				     uint32_t *d_out_len, uint32_t *d_status, u32 only, int s);
+
 int gpumt_brotli_decompress_batch(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off,
 				  const uint32_t *d_rec_len, size_t nrec, void *d_out,
 				  const uint64_t *d_out_off, const uint32_t *d_out_cap,
 				  uint32_t *d_out_len, uint32_t *d_status, int s)
+{
+	return brotli_decompress_records(h, d_stream, d_rec_off, d_rec_len, nrec, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+					 0xFFFFFFFFu, s);
+}
+
+static int brotli_decompress_records(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off, const uint32_t *d_rec_len,
+				     size_t nrec, void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+				     uint32_t *d_out_len, uint32_t *d_status, u32 only, int s)
 {
 	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
 		return GPUMT_E_ARG;
@@ -2553,12 +2627,17 @@ int gpumt_brotli_decompress_batch(gpumt_ctx *h, const void *d_stream, const uint
 	 * twice as slow as a one-record wave.  That wins as soon as the one-record kernel would need more than one round of
 	 * its resident waves (8 192 records: 283 ms against 500), and loses below (1 024 records: 308 ms against 151), so
 	 * the batch size chooses.  bdec_variant: 0 = that rule, 1 = the general kernel alone, 2 = dec4 first whatever the size */
-	u32 want = 0xFFFFFFFFu;
+	u32 want = only;
 	const bool use4 = h->bdec_variant == 2 || (h->bdec_variant == 0 && nrec > (size_t)h->bdec_waves);
 	if (use4 && h->profile != 7) {
-		hipLaunchKernelGGL(zmt_brotli_dec4_kernel, dim3((unsigned)((nrec + B4_NG - 1) / B4_NG)), dim3(64), 0, h->st[s],
-				   (const u8 *)d_stream, d_rec_off, d_rec_len, (u32)nrec, (u8 *)d_out, d_out_off, d_out_cap,
-				   d_out_len, d_status);
+		if (only == 0xFFFFFFFFu)
+			hipLaunchKernelGGL(zmt_brotli_dec4_kernel, dim3((unsigned)((nrec + B4_NG - 1) / B4_NG)), dim3(64), 0, h->st[s],
+					   (const u8 *)d_stream, d_rec_off, d_rec_len, (u32)nrec, (u8 *)d_out, d_out_off, d_out_cap,
+					   d_out_len, d_status);
+		else
+			hipLaunchKernelGGL(zmt_brotli_dec4_wanted_kernel, dim3((unsigned)((nrec + B4_NG - 1) / B4_NG)), dim3(64), 0,
+					   h->st[s], (const u8 *)d_stream, d_rec_off, d_rec_len, (u32)nrec, (u8 *)d_out, d_out_off,
+					   d_out_cap, d_out_len, d_status, only);
 		want = 102u;
 	}
 	if (h->profile == 7)
@@ -2572,6 +2651,113 @@ int gpumt_brotli_decompress_batch(gpumt_ctx *h, const void *d_stream, const uint
 	PROF1(12);
 	CK(hipGetLastError());
 	return GPUMT_OK;
+}
+
+/* gpumt_lz4_decompress_batch_par's structure with the span stages of brotli_dec_rec.h in front of the record decoders */
+int gpumt_brotli_decompress_batch_par(gpumt_ctx *h, const void *d_stream, const uint64_t *d_rec_off, const uint32_t *d_rec_len,
+				      size_t nrec, void *d_out, const uint64_t *d_out_off, const uint32_t *d_out_cap,
+				      uint32_t *d_out_len, uint32_t *d_status, uint32_t *d_rec_par, int s)
+{
+	static_assert(sizeof(BRec) == 32 && sizeof(B4Span) == 32, "record layout");
+	if (!h || !STREAM_OK(s) || nrec == 0 || nrec > 0x3FFFFFFFu)
+		return GPUMT_E_ARG;
+	if (use(h))
+		return GPUMT_E_HIP;
+	const hipStream_t st = h->st[s];
+	if (d_rec_par)
+		CK(hipMemsetAsync(d_rec_par, 0, nrec * 4, st));
+	/* the stage's own areas.  Per record: the plan and the first span.  Per slice, sized once the plans are known: the span
+	 * table and a status word per span */
+	const size_t rec_bytes = (nrec * sizeof(BRec) + 255) & ~(size_t)255, word_bytes = (nrec * 4 + 255) & ~(size_t)255;
+	const size_t need_a = rec_bytes + word_bytes;
+	const size_t cap = h->brec_cap_mb ? (size_t)h->brec_cap_mb << 20 : ~(size_t)0;
+	int par = h->brec_par, fallback = 0;
+	if (par && ((h->brec_refused && need_a >= h->brec_refused) || need_a > cap ||
+		    zrec_want(h, &h->brec_area[s], &h->brec_bytes[s], need_a, st))) {
+		h->brec_refused = need_a;
+		par = 0;
+		fallback = 1;
+	}
+	if (par && rec_bytes > h->brec_pin_bytes[s]) {
+		/* (the copy that read the old area was waited for by the call that queued it) */
+		void *p = NULL;
+		if (hipHostMalloc(&p, rec_bytes, hipHostMallocDefault) != hipSuccess || !p) {
+			(void)hipGetLastError();
+			h->brec_refused = need_a;
+			par = 0;
+			fallback = 1;
+		} else {
+			if (h->brec_pin[s])
+				(void)hipHostFree(h->brec_pin[s]);
+			h->brec_pin[s] = p;
+			h->brec_pin_bytes[s] = rec_bytes;
+		}
+	}
+	size_t npar = 0, nspans = 0, nslices = 0, max_span = 0, kept = 0;
+	BRec *recs = (BRec *)h->brec_area[s];
+	u32 *ufirst = par ? (u32 *)((u8 *)recs + rec_bytes) : NULL;
+	const BRec *hrec = (const BRec *)h->brec_pin[s];
+	const dim3 per_rec((unsigned)((nrec + 255) / 256)), tpb(256);
+	BRecSlice S;
+	if (par) {
+		hipLaunchKernelGGL(zmt_brotli_rec_plan_kernel, per_rec, tpb, 0, st, (const u8 *)d_stream, d_rec_off, d_rec_len, (u32)nrec,
+				   d_out_off, d_out_cap, (u32)h->brec_min_spans, recs);
+		/* one round trip: the host sizes the span table and the launches of the execute stage from the plans */
+		CK(hipMemcpyAsync(h->brec_pin[s], recs, nrec * sizeof(BRec), hipMemcpyDeviceToHost, st));
+		CK(hipStreamSynchronize(st));
+		for (size_t at = 0; brec_next_slice(hrec, nrec, at, BREC_SLICE_SPANS, &S); at = S.b) {
+			nspans += S.nspan;
+			nslices++;
+			max_span = S.nspan > max_span ? S.nspan : max_span;
+		}
+		for (size_t i = 0; i < nrec; i++)
+			npar += hrec[i].flags & BREC_ELIGIBLE;
+		const size_t need_b = (max_span * (sizeof(B4Span) + 4) + 255) & ~(size_t)255, need = need_a + need_b;
+		if (nslices && ((h->brec_refused && need >= h->brec_refused) || need > cap ||
+				zrec_want(h, &h->brec_tab[s], &h->brec_tab_bytes[s], need_b, st))) {
+			h->brec_refused = need;
+			par = 0;
+			fallback = 1;
+		}
+	}
+	if (!par || !nslices) {
+		/* nothing for the span stages (or no room for them): the serial call */
+		if (h->trace >= 1)
+			fprintf(stderr, "[gpumt brotli rec] records %zu par 0 spans 0 kept 0 fallback %d\n", nrec, fallback);
+		return brotli_decompress_records(h, d_stream, d_rec_off, d_rec_len, nrec, d_out, d_out_off, d_out_cap, d_out_len,
+						 d_status, 0xFFFFFFFFu, s);
+	}
+	B4Span *spans = (B4Span *)h->brec_tab[s];
+	u32 *span_st = (u32 *)(spans + max_span);
+	/* every record is the record decoders' until finish says it was kept */
+	CK(hipMemsetD32Async((hipDeviceptr_t)d_status, (int)BREC_TODO, nrec, st));
+	for (size_t at = 0; brec_next_slice(hrec, nrec, at, BREC_SLICE_SPANS, &S); at = S.b) {
+		const u32 n = (u32)(S.b - S.a);
+		const dim3 per_slice((n + 255) / 256);
+		hipLaunchKernelGGL(zmt_brotli_rec_scan_kernel, dim3(1), tpb, 0, st, (const BRec *)(recs + S.a), n, ufirst + S.a);
+		hipLaunchKernelGGL(zmt_brotli_rec_table_kernel, per_slice, tpb, 0, st, (const u8 *)d_stream, (const BRec *)(recs + S.a), n,
+				   (u32)S.a, (const u32 *)(ufirst + S.a), S.nspan, spans);
+		hipLaunchKernelGGL(zmt_brotli_dec4_span_kernel, dim3((S.nspan + B4_NG - 1) / B4_NG), dim3(64), 0, st, (const u8 *)d_stream,
+				   (const B4Span *)spans, S.nspan, (u8 *)d_out, span_st);
+		hipLaunchKernelGGL(zmt_brotli_rec_finish_kernel, per_slice, tpb, 0, st, (const BRec *)(recs + S.a), n,
+				   (const u32 *)(ufirst + S.a), S.nspan, (const B4Span *)spans, (const u32 *)span_st, d_out_len + S.a,
+				   d_status + S.a,
+				   d_rec_par ? d_rec_par + S.a : (u32 *)NULL);
+	}
+	CK(hipGetLastError());
+	if (h->trace >= 1) {
+		/* (the count of kept records costs a round trip: the trace alone pays it) */
+		u32 *hst = (u32 *)malloc(nrec * 4);
+		if (hst && hipMemcpyAsync(hst, d_status, nrec * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+		    hipStreamSynchronize(st) == hipSuccess)
+			for (size_t i = 0; i < nrec; i++)
+				kept += hst[i] == GPUMT_ST_OK;
+		free(hst);
+		fprintf(stderr, "[gpumt brotli rec] records %zu par %zu spans %zu kept %zu fallback 0\n", nrec, npar, nspans, kept);
+	}
+	/* everything the span stages did not keep is decoded and judged by the record decoders */
+	return brotli_decompress_records(h, d_stream, d_rec_off, d_rec_len, nrec, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+					 BREC_TODO, s);
 }
 
 /* ---- snappy-mt (snappy.hip): persistent waves, one record at a time ---- */
@@ -2793,6 +2979,22 @@ int gpumt_set_variant(gpumt_ctx *h, const char *what, int variant)
 		prev = h->lrec_cap_mb;
 		h->lrec_cap_mb = variant;
 		h->lrec_refused = 0; /* (a new cap: ask again) */
+	} else if (!strcmp(what, "brotli_rec_par")) {
+		if (variant != 0 && variant != 1)
+			return -1;
+		prev = h->brec_par;
+		h->brec_par = variant;
+	} else if (!strcmp(what, "brotli_rec_min_spans")) {
+		if (variant < 2 || variant > 65536)
+			return -1;
+		prev = h->brec_min_spans;
+		h->brec_min_spans = variant;
+	} else if (!strcmp(what, "brotli_rec_cap_mb")) {
+		if (variant < 0)
+			return -1;
+		prev = h->brec_cap_mb;
+		h->brec_cap_mb = variant;
+		h->brec_refused = 0; /* (a new cap: ask again) */
 	} else if (!strcmp(what, "snappy_dec")) {
 		prev = h->sdec_variant;
 		h->sdec_variant = variant;

@@ -495,11 +495,13 @@ class Engine:
                 b.free()
         return raw[:total].tobytes(), status, rec_par
 
-    def brotli_compress(self, d_in, n, chunk, d_slots, stride, d_rec_len, stream=0, level=1, win=False):
-        """win=True: gpumt_brotli_compress_batch_win, the whole chunk as the match window from quality 9 on"""
-        call = self.L.gpumt_brotli_compress_batch_win if win else self.L.gpumt_brotli_compress_batch_level
-        self._ck(call(self.h, d_in.ptr, int(n), int(chunk), d_slots.ptr, int(stride), d_rec_len.ptr, int(level), stream),
-                 "brotli_compress_batch_win" if win else "brotli_compress_batch_level")
+    def brotli_compress(self, d_in, n, chunk, d_slots, stride, d_rec_len, stream=0, level=1, win=False, index=False):
+        """win=True: gpumt_brotli_compress_batch_win, the whole chunk as the match window from quality 9 on;
+        index=True: gpumt_brotli_compress_batch_index, the table encoders' records with a span index"""
+        assert not (win and index), "the window encoder writes no index"
+        name = "brotli_compress_batch_" + ("win" if win else "index" if index else "level")
+        call = getattr(self.L, "gpumt_" + name)
+        self._ck(call(self.h, d_in.ptr, int(n), int(chunk), d_slots.ptr, int(stride), d_rec_len.ptr, int(level), stream), name)
 
     def brotli_win_depth(self, level):
         return int(self.L.gpumt_brotli_win_depth(int(level)))
@@ -509,6 +511,14 @@ class Engine:
         self._ck(self.L.gpumt_brotli_decompress_batch(self.h, d_stream.ptr, d_rec_off.ptr, d_rec_len.ptr, nrec,
                                                       d_out.ptr, d_out_off.ptr, d_out_cap.ptr, d_out_len.ptr,
                                                       d_status.ptr, stream), "brotli_decompress_batch")
+
+    def brotli_decompress_par(self, d_stream, d_rec_off, d_rec_len, nrec, d_out, d_out_off, d_out_cap, d_out_len,
+                              d_status, d_rec_par, stream=0):
+        """gpumt_brotli_decompress_batch_par: indexed records span by span, the rest by the record decoders"""
+        self._ck(self.L.gpumt_brotli_decompress_batch_par(self.h, d_stream.ptr, d_rec_off.ptr, d_rec_len.ptr, nrec,
+                                                          d_out.ptr, d_out_off.ptr, d_out_cap.ptr, d_out_len.ptr,
+                                                          d_status.ptr, d_rec_par.ptr if d_rec_par is not None else None,
+                                                          stream), "brotli_decompress_batch_par")
 
     # snappy-mt (include/gpumt.h gpumt_snappy_*): same call shapes as brotli
     def snappy_slot_stride(self, chunk):
@@ -554,10 +564,54 @@ class Engine:
             recs.append(raw[o:o + n].tobytes())
         return recs, status
 
+    def brotli_decompress_par_bytes(self, stream: bytes, rec_off, rec_len, cap, out_off=None, par=True):
+        """brotli_decompress_bytes through gpumt_brotli_decompress_batch_par -> (list of decoded records, status[n],
+        out_len[n], rec_par[n]).  out_off: where each record's output area starts (default: back to back); every byte
+        outside the areas must come back untouched.  par=False: the serial call in the same layout (rec_par all 0)."""
+        nrec = len(rec_off)
+        cap = np.asarray(cap, np.uint32)
+        if out_off is None:
+            out_off = np.zeros(nrec, np.uint64)
+            out_off[1:] = np.cumsum(cap.astype(np.uint64))[:-1]
+        out_off = np.asarray(out_off, np.uint64)
+        total = max(int(o) + int(c) for o, c in zip(out_off, cap))
+        d_stream = self.upload(stream + b"\0" * 256)
+        d_ro, d_rl = self.upload(np.asarray(rec_off, np.uint64).copy()), self.upload(np.asarray(rec_len, np.uint32).copy())
+        d_oo, d_oc = self.upload(out_off.copy()), self.upload(cap.copy())
+        d_ol, d_st = self.upload(np.full(nrec, 0xFFFFFFFF, np.uint32)), self.upload(np.full(nrec, 99, np.uint32))
+        d_rp = self.upload(np.full(nrec, 7, np.uint32))
+        d_out = self.upload(np.full(total + 64, 0xCC, np.uint8))
+        try:
+            if par:
+                self.brotli_decompress_par(d_stream, d_ro, d_rl, nrec, d_out, d_oo, d_oc, d_ol, d_st, d_rp)
+                rec_par = self.download(d_rp, nrec * 4, np.uint32)
+            else:
+                self.brotli_decompress(d_stream, d_ro, d_rl, nrec, d_out, d_oo, d_oc, d_ol, d_st)
+                rec_par = np.zeros(nrec, np.uint32)
+            status = self.download(d_st, nrec * 4, np.uint32)
+            out_len = self.download(d_ol, nrec * 4, np.uint32)
+            raw = self.download(d_out, total + 64)
+        finally:
+            for b in (d_stream, d_ro, d_rl, d_oo, d_oc, d_ol, d_st, d_rp, d_out):
+                b.free()
+        inside = np.zeros(total + 64, bool)
+        recs = []
+        for i in range(nrec):
+            o, n = int(out_off[i]), int(out_len[i]) if status[i] == 0 else 0
+            assert n <= int(cap[i])
+            inside[o:o + int(cap[i])] = True
+            if status[i] == 0:
+                assert (raw[o + n:o + int(cap[i])] == 0xCC).all(), "wrote past the decoded size"
+            recs.append(raw[o:o + n].tobytes())
+        assert (raw[~inside] == 0xCC).all(), "decoder wrote outside the records' output areas"
+        return recs, status, out_len, rec_par
+
     # ---- convenience round trips on host bytes (tests) ----------------------------------------
-    def compress_bytes(self, data: bytes, chunk: int, codec="lz4", level=1, win=False):
-        """-> (stream bytes, rec_off[n+1] u64, rec_len[n] u32); win: codec "zstd" or "brotli" with the whole-chunk window"""
+    def compress_bytes(self, data: bytes, chunk: int, codec="lz4", level=1, win=False, index=False):
+        """-> (stream bytes, rec_off[n+1] u64, rec_len[n] u32); win: codec "zstd" or "brotli" with the whole-chunk window;
+        index: codec "brotli" with the span index of gpumt_brotli_compress_batch_index"""
         assert not win or codec in ("zstd", "brotli")
+        assert not index or codec == "brotli"
         n = len(data)
         nrec = self.record_count(n, chunk)
         stride = self.zstd_slot_stride(chunk) if codec in ("zstd", "brotli") else self.slot_stride(chunk)
@@ -569,7 +623,7 @@ class Engine:
             if codec == "zstd":
                 self.zstd_compress(d_in, n, chunk, d_slots, stride, d_len, level=level, win=win)
             elif codec == "brotli":
-                self.brotli_compress(d_in, n, chunk, d_slots, stride, d_len, level=level, win=win)
+                self.brotli_compress(d_in, n, chunk, d_slots, stride, d_len, level=level, win=win, index=index)
             else:
                 self.lz4_compress(d_in, n, chunk, d_slots, stride, d_len, level=level)
             rec_len = self.download(d_len, nrec * 4, np.uint32)
